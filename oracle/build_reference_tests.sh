@@ -3,8 +3,8 @@
 # unit tests and micro-benchmark mains under test/ -- unchanged -- against
 # include/graphblas/graphblas.hpp and links them to libgrb_hip.so.  Boost.Test and
 # Boost.ProgramOptions are absent from the image; include/boost/ holds the few macros / classes
-# these sources touch.  Outputs go to build/refcheck/tests/ (git-ignored; travels to the GPU box,
-# where tests/test_gpu_reftests.py runs them).
+# these sources touch.  Outputs go to oracle/_ref/refcheck/tests/ (git-ignored like the rest of
+# oracle/_ref/, and kept with the tree: tests/test_gpu_reftests.py runs them).
 #
 # Left out, and why:
 #   gassign gvector gmmio gutil gsparsematrix  stale: they do not compile against the reference's
@@ -17,11 +17,11 @@ set -e
 REF=${REF:-/root/reference}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 [ -d "$REF/test" ] || { echo "no reference tree, skipping"; exit 0; }
-mkdir -p "$ROOT/build/refcheck/tests"
+mkdir -p "$ROOT/oracle/_ref/refcheck/tests"
 for t in gvxm greduce gewiseadd gewisemult gtrace gdensevector gsparsevector gdescriptor gbinaryop \
          gspmspv gpush gpull gpushbench gpullbench gspmvbench gspmspvbench; do
   g++ -std=c++11 -O0 -fpermissive -w -x c++ -I"$ROOT/include" -I"$REF" "$REF/test/$t.cu" \
-      -L"$ROOT/graphblast_amd" -lgrb_hip -Wl,-rpath,'$ORIGIN/../../../graphblast_amd' \
-      -o "$ROOT/build/refcheck/tests/${t}_ref"
-  echo "built build/refcheck/tests/${t}_ref"
+      -L"$ROOT/graphblast_amd" -lgrb_hip -Wl,-rpath,'$ORIGIN/../../../../graphblast_amd' \
+      -o "$ROOT/oracle/_ref/refcheck/tests/${t}_ref"
+  echo "built oracle/_ref/refcheck/tests/${t}_ref"
 done

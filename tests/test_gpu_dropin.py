@@ -1,6 +1,6 @@
 """GPU suite: the reference's own applications (example/gbfs.cu, gsssp.cu, gpr.cu -- their
 main(), their algorithm/*.hpp loops and their CPU verification), compiled UNCHANGED in the
-build container against include/graphblas/graphblas.hpp (tools/build_reference_examples.sh),
+build container against include/graphblas/graphblas.hpp (oracle/build_reference_examples.sh),
 run here on the reference's data/small graphs.  Each prints CORRECT / INCORRECT itself
 (test/test.hpp:60-114)."""
 import os
@@ -10,7 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "build", "refcheck")
+BIN = os.path.join(ROOT, "oracle", "_ref", "refcheck")
 import shutil
 import tempfile
 
@@ -26,7 +26,7 @@ for _f in os.listdir(_SRC):
 def _run(exe, *args):
     path = os.path.join(BIN, exe)
     if not os.path.exists(path):
-        pytest.skip("build/refcheck/%s not built (needs the reference tree at build time)" % exe)
+        pytest.skip("oracle/_ref/refcheck/%s not built (needs the reference tree at build time)" % exe)
     out = subprocess.run([path] + list(args), capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     return out.stdout
@@ -184,7 +184,7 @@ def test_c_abi_example_runs(tmp_path):
 def _run_env(exe, env, *args):
     path = os.path.join(BIN, exe)
     if not os.path.exists(path):
-        pytest.skip("build/refcheck/%s not built" % exe)
+        pytest.skip("oracle/_ref/refcheck/%s not built" % exe)
     e = dict(os.environ)
     e.update(env)
     out = subprocess.run([path] + list(args), capture_output=True, text=True, timeout=600, cwd=ROOT, env=e)

@@ -350,7 +350,7 @@ def test_bench_n_greater_than_one_path_with_two_ranks_on_one_gpu():
     env = dict(os.environ, GRB_BENCH_SHARED_GPU="1", GRB_NUM_CU="112")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "4", "--warmup", "1", "--scale", "16", "--no-cpu-baseline"],
+                          "--gpus", "2", "--steps", "4", "--warmup", "1", "--scale", "16", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=500, cwd=root, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

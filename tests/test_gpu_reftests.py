@@ -1,7 +1,7 @@
 """GPU suite: the reference's own unit tests (test/gvxm.cu, greduce.cu, gewiseadd.cu, gewisemult.cu,
 gtrace.cu, gdensevector.cu, gsparsevector.cu, gdescriptor.cu, gbinaryop.cu) and its smoke /
 micro-benchmark mains (gspmspv, gpush, gpull, g*bench), compiled UNCHANGED in the build container
-against include/graphblas/graphblas.hpp (tools/build_reference_tests.sh) and run here.  Their
+against include/graphblas/graphblas.hpp (oracle/build_reference_tests.sh) and run here.  Their
 assertions (BOOST_ASSERT_LIST: exact element-wise comparison against the inline CPU loops and
 literals of each test) abort the process on the first mismatch."""
 import os
@@ -12,7 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "build", "refcheck", "tests")
+BIN = os.path.join(ROOT, "oracle", "_ref", "refcheck", "tests")
 DATA = os.path.join(ROOT, "tests", "golden", "data")
 
 

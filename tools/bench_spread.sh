@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT 2>/dev/null || cd "$(dirname "$0")/.."
 N=${1:-10}; O=${2:-gpurun_out/bench_spread}; mkdir -p $O
 for i in $(seq 1 $N); do
-  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-refrule > $O/run_$i.log 2> $O/run_$i.err
+  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-batch --no-refrule > $O/run_$i.log 2> $O/run_$i.err
 done
 python - $O $N <<'PY'
 import json, sys, statistics as st
@@ -25,7 +25,7 @@ for i in range(1, N + 1):
 with open(O + "/spread.jsonl", "w") as f:
     for r in rows: f.write(json.dumps(r) + "\n")
 v = [r["ms_per_step"] for r in rows]; b = [r["blocking_ms_per_step"] for r in rows]; k = [r["kernel_ms_by_hip_events"] for r in rows]
-print("command: python bench.py --gpus 1 --steps 20 --warmup 5 (fresh process each), %d runs" % len(rows))
+print("command: python bench.py --gpus 1 --steps 20 --warmup 5 --full (fresh process each), %d runs" % len(rows))
 print("queued   ms_per_step min %.4f median %.4f max %.4f   TEPS median %.4g" % (min(v), st.median(v), max(v), st.median([r["value"] for r in rows])))
 print("blocking ms_per_step min %.4f median %.4f max %.4f" % (min(b), st.median(b), max(b)))
 print("kernel by HIP events  min %.4f median %.4f max %.4f" % (min(k), st.median(k), max(k)))

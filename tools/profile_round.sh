@@ -1,11 +1,11 @@
 # The rocprofv3 passes behind profiles/rNN (run on the GPU box through gpurun; outputs under gpurun_out/).
 #   usage: bash tools/profile_round.sh prof_r3
-# 1. plain `python bench.py`                       -> bench_plain.log (the JSON line)
+# 1. `python bench.py --full`                       -> bench_plain.log (the JSON line)
 # 2. the same command under --kernel-trace --stats -> per-kernel statistics + the kernel trace (kept: the
 #    default command also times the reference's direction rule and the 64-source sweep AFTER the main
 #    measurement; tools/summarize_profiles.py splits bfs_persistent_kernel's launches by order)
 # 3. two separate --pmc passes (FETCH_SIZE / WRITE_SIZE need different counter slots), each with
-#    --kernel-trace only, over `bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-refrule` (the 64-source
+#    --kernel-trace only, over `bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-refrule` (the 64-source
 #    sweep and the sparse x dense product included, so their kernels get counters too)
 # 4. BASELINE.json's other configurations: the plain JSON line, a --kernel-trace --stats run and the same two --pmc
 #    passes each (`--no-cpu-baseline`); PROFILE_WORKLOADS="" skips them (their kernels unchanged since the last take),
@@ -28,12 +28,12 @@ with open(sys.argv[2], "w", newline="") as f:
 PY
 }
 if [ -z "$PROFILE_SKIP_DEFAULT" ]; then
-timeout 300 python bench.py > $P/bench_plain.log 2> $P/bench_plain.err
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -o bench -- python bench.py > $P/bench_stdout.log 2> $P/stats.err
+timeout 300 python bench.py --full > $P/bench_plain.log 2> $P/bench_plain.err
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -o bench -- python bench.py --full > $P/bench_stdout.log 2> $P/stats.err
 for f in $(find $P/stats -name "bench_kernel_stats.csv"); do cp $f $P/bench_kernel_stats.csv; done
 for f in $(find $P/stats -name "bench_kernel_trace.csv"); do grb_trace "$f" "$P/bench_kernel_trace_grb.csv"; done
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $P/pmc_$C -o p -- python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-refrule > $P/pmc_$C.log 2>&1
+  timeout 500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $P/pmc_$C -o p -- python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-refrule > $P/pmc_$C.log 2>&1
   for f in $(find $P/pmc_$C -name "p_counter_collection.csv"); do cp $f $P/pmc_$C/p_counter_collection.csv 2>/dev/null; done
 done
 fi

@@ -28,7 +28,7 @@ with open(dst + '/bench_kernel_stats_grb.csv', 'w', newline='') as f:
             w.writerow(r)
 shutil.copy(src + '/bench_stdout.log', dst + '/bench_stdout_under_rocprof.log')
 shutil.copy(src + '/bench_plain.log', dst + '/bench_stdout.log')
-# ---- bfs_persistent_kernel by phase of the default command.  Launch order in bench.py: W warm-up, K timed, K with HIP
+# ---- bfs_persistent_kernel by phase of the --full command.  Launch order in bench.py: W warm-up, K timed, K with HIP
 # events (the roofline pass), then accounting / reference-rule / spot-check launches.  The whole-run mean in the stats
 # file mixes them (the reference-rule launches run 2x longer by design); the timed region is launches [W, W + K).
 trace = src + '/bench_kernel_trace_grb.csv'
@@ -60,7 +60,7 @@ if os.path.exists(trace):
         E += max(line["warmup"], 2) + K + 2 + K
     if "coscheduled" in line:                # ... its launches are other kernels, but K one-at-a-time steps follow it
         E += K
-    ph = {"source": "rocprofv3 --kernel-trace of the default `python bench.py` (same run as bench_kernel_stats_*.csv)",
+    ph = {"source": "rocprofv3 --kernel-trace of `python bench.py --full` (same run as bench_kernel_stats_*.csv)",
           "warmup": W, "steps": K, "bfs_persistent_kernel_launches": len(bfs),
           "bfs_persistent_kernel_mean_us": {
               "timed_region_launches_W_to_W+K": round(sum(bfs[W:W + K]) / K / 1e3, 2),
@@ -182,7 +182,7 @@ for W in ALL_W:
 if lines:
     open(dst + '/other_workloads.jsonl', 'w').write("\n".join(lines) + "\n")
 doc = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, each with --kernel-trace only) over "
-                 "`python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-refrule` on MI355X",
+                 "`python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-refrule` on MI355X",
        "note": "hbm_bytes_per_launch = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 B.  The factor 2 on reads is MI355X_MICROARCH.md's gfx950 "
                "correction (128-B requests tallied at 64 B), calibrated in this same run on this library's own 4 B/lane kernels of "
                "known byte count (`calibration`: the 64 Mi-float reduce reads 262144 KB, eWiseAdd 524288 KB, assign 262144 KB; each is "
