@@ -150,7 +150,9 @@ extern "C" grb_info grb_bfs_fused_enqueue(grb_vector v, grb_matrix A, grb_index 
     if (li != GRB_NOT_IMPLEMENTED && li != GRB_PANIC) return li;
   }
   // a traversal the ring does not serve (road-network queues, CSR-only format, the host-driven fallback): run it now
-  // and park the result; the ticket behaves the same
+  // and park the result; the ticket behaves the same.  Traversals that have gathered for a launch go first (one of them
+  // may write the same vector: the one queued last must win)
+  GRB_TRY(bfs_co_flush());
   grb_bfs_result res = {};
   GRB_TRY(grb_bfs_fused(v, A, source, desc, &res, nullptr, 0, 0));
   seq = ++ctx().mail_seq;

@@ -1342,7 +1342,8 @@ struct CoPend {                                  // a traversal that has its tic
                                                  // the rules it was queued under, and one launch serves one set of rules)
 };
 struct BfsRing {
-  int co_width = 1;                              // traversals per launch (grb_bfs_set_coschedule); 1: every traversal its own launch
+  int co_width = 0;                              // traversals per launch (grb_bfs_set_coschedule): 0 (the default) the width rule
+                                                 // (co_grids) picks it; 1 every traversal its own launch; k fixed
   int co_n = 0;                                  // ... and the ones that wait for the launch to fill (ticket state 3)
   CoPend co[kCoTrain];
   BfsLane lane[kMaxLanes + 1 + kCoMax];          // [0]: the library's stream (blocking calls, one lane); [1 ..]: the lanes proper;
@@ -1410,13 +1411,90 @@ grb_info ring_wait(int slot, int seq, unsigned int* out, hipStream_t stream) {
 
 // Queues one traversal on the library's stream; its record will appear in ring slot `slot` under
 // tag *seq_out.
+static size_t lane_alloc_bytes(size_t bytes) { return (bytes + bytes / 4 + 255) & ~(size_t)255; }
 static grb_info lane_buffer(void** p, size_t* cap, size_t bytes, hipStream_t s) {
   if (*cap >= bytes) return GRB_SUCCESS;
   if (*p) { GRB_HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(*p); *p = nullptr; *cap = 0; }
-  const size_t want = (bytes + bytes / 4 + 255) & ~(size_t)255;
+  const size_t want = lane_alloc_bytes(bytes);
   GRB_HIP_TRY(hipMalloc(p, want));
   *cap = want;
   return GRB_SUCCESS;
+}
+
+// What a lane's buffers hold for a traversal of A: the state blocks (two for one traversal per launch, three for a
+// sub-grid of a launch of several), V1, the big-vertex list, the level records.
+struct LaneSizes {
+  int nwords = 0, big_cap = 0, rec_cap = 0;
+  size_t st_bytes = 0, block_bytes = 0, zero_bytes = 0, v1_bytes = 0, big_bytes = 0, rec_bytes = 0;
+};
+static LaneSizes lane_sizes(grb_matrix A, bool co) {
+  LaneSizes z;
+  z.nwords = 2 * ceil_div(A->nrows, 64);
+  z.rec_cap = 1 << 15;
+  z.big_cap = (int)(A->nvals / kBigDeg) + 2;
+  // one allocation: the blocks [state | V0 | F0 .. F(kKeep + 2)], used in rotation (PersistArgs::blocks)
+  z.st_bytes = (sizeof(PersistState) + 255) & ~(size_t)255;
+  z.block_bytes = (z.st_bytes + 4 * (size_t)(1 + kKeep + 3) * (size_t)z.nwords + 255) & ~(size_t)255;
+  z.zero_bytes = (co ? 3 : 2) * z.block_bytes;
+  z.v1_bytes = 4 * (size_t)z.nwords;
+  z.big_bytes = sizeof(int2) * (size_t)z.big_cap;
+  z.rec_bytes = sizeof(grb_bfs_level) * (size_t)z.rec_cap;
+  return z;
+}
+// Gives lane `lane_id` its buffers for z (kept when they are large enough) and, when they are new or were last cleared
+// for a graph of another size, clears every block and the rotation words -- memsets on s.
+static grb_info lane_provide(int lane_id, const LaneSizes& z, hipStream_t s) {
+  BfsLane& ln = g_ring.lane[lane_id];
+  if (!ln.d_rot) {
+    GRB_HIP_TRY(hipMalloc((void**)&ln.d_rot, 256));
+    GRB_HIP_TRY(hipMemset(ln.d_rot, 0, 256));
+  }
+  const size_t had = ln.zero_cap;
+  GRB_TRY(lane_buffer(&ln.zero, &ln.zero_cap, z.zero_bytes, s));
+  GRB_TRY(lane_buffer(&ln.v1, &ln.v1_cap, z.v1_bytes, s));
+  GRB_TRY(lane_buffer(&ln.big, &ln.big_cap, z.big_bytes, s));
+  GRB_TRY(lane_buffer(&ln.rec, &ln.rec_cap, z.rec_bytes, s));
+  if (had != ln.zero_cap || ln.clean_bytes != z.zero_bytes) {     // new memory, or a graph of another size: clear every block
+    GRB_HIP_TRY(hipMemsetAsync(ln.zero, 0, z.zero_bytes, s));
+    GRB_HIP_TRY(hipMemsetAsync(ln.d_rot, 0, 16, s));
+    ln.block = 0;
+    ln.clean_bytes = z.zero_bytes;
+  }
+  return GRB_SUCCESS;
+}
+static bool lane_is_ready(int lane_id, const LaneSizes& z) {
+  const BfsLane& ln = g_ring.lane[lane_id];
+  return ln.d_rot && ln.zero_cap >= z.zero_bytes && ln.v1_cap >= z.v1_bytes && ln.big_cap >= z.big_bytes &&
+         ln.rec_cap >= z.rec_bytes && ln.clean_bytes == z.zero_bytes;
+}
+
+// Sub-grids of the launches of several traversals: the first such launch on a graph of a given size provisions every
+// sub-grid the width rule can use (`want`) -- buffers and cleared blocks -- so that no later launch on that graph
+// allocates or clears anything in front of its kernel.  New memory is bounded by a quarter of what the device has free
+// (hipMemGetInfo); an allocation that fails all the same ends the provisioning there, with the HIP error cleared.
+// Returns how many sub-grids are ready, 0 .. want: the launch's width is capped by it.
+static int co_provision(grb_matrix A, int want) {
+  const LaneSizes z = lane_sizes(A, true);
+  int ready = 0;
+  while (ready < want && lane_is_ready(kMaxLanes + 1 + ready, z)) ++ready;
+  if (ready == want) return ready;                         // (every launch after the first on a graph)
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return ready; }
+  const size_t per_grid = lane_alloc_bytes(z.zero_bytes) + lane_alloc_bytes(z.v1_bytes) + lane_alloc_bytes(z.big_bytes) +
+                          lane_alloc_bytes(z.rec_bytes) + 256;
+  size_t budget = free_b / 4;
+  hipStream_t s = ctx().stream;
+  for (int j = ready; j < want; ++j) {
+    const BfsLane& ln = g_ring.lane[kMaxLanes + 1 + j];
+    const bool grows = ln.zero_cap < z.zero_bytes || ln.v1_cap < z.v1_bytes || ln.big_cap < z.big_bytes || ln.rec_cap < z.rec_bytes;
+    if (grows) {
+      if (budget < per_grid) break;
+      budget -= per_grid;
+    }
+    if (lane_provide(kMaxLanes + 1 + j, z, s) != GRB_SUCCESS) { (void)hipGetLastError(); break; }
+    ready = j + 1;
+  }
+  return ready;
 }
 
 // What a launch needs besides its argument block: whose buffers it runs on and what to note once it is queued.
@@ -1430,6 +1508,28 @@ struct LaunchCtx {
   int* p_blocksel = nullptr;     // one traversal per launch: the host's side of the rotation
 };
 
+// The owner-computes tables of a narrower grid (a lane's, or the 128-thread sub-grids' narrower slices): one set per
+// matrix, made again when another grid asks (the ranges are cut per workgroup).
+static grb_info oc2_tables_ensure(grb_matrix A, int G, int oc_words) {
+  const int oc2_key = G + (oc_words << 12);
+  if (A->oc2_state != 0 && A->oc2_grid == oc2_key) return GRB_SUCCESS;
+  if (A->d_oc2_bounds || A->d_oc2_off || A->d_oc2_bigidx) {
+    GRB_HIP_TRY(hipDeviceSynchronize());               // (traversals of other lanes may be reading the old tables)
+    (void)hipFree(A->d_oc2_bounds); (void)hipFree(A->d_oc2_off); (void)hipFree(A->d_oc2_bigidx);
+    A->d_oc2_bounds = nullptr; A->d_oc2_off = nullptr; A->d_oc2_bigidx = nullptr;
+  }
+  A->oc2_state = -1;
+  A->oc2_grid = oc2_key;
+  const Index n = A->nrows;
+  if (A->nvals > 0 && (Index)A->h_csr_ptr.size() == n + 1) {
+    GRB_TRY(oc_tables_build(A->csr.ptr, A->csr.ind, A->h_csr_ptr, n, n, G, &A->d_oc2_bounds, &A->d_oc2_off, &A->d_oc2_bigidx,
+                            &A->oc2_nb, &A->oc2_nrows, oc_words));
+    if (A->d_oc2_off) A->oc2_state = 1;
+    GRB_HIP_TRY(hipStreamSynchronize(ctx().stream));   // (built on the library's stream; the lanes read them)
+  }
+  return GRB_SUCCESS;
+}
+
 // Fills the argument block of one (sub-)grid: the lane's buffers (lane 0: the library's scratch slots), the once-per-
 // matrix facts and tables.  Queues at most memsets on lc->s.
 static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int profile, int lane_id, bool co, PersistArgs* out,
@@ -1438,19 +1538,15 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
   GRB_TRY(ring_init());
   Context& c = ctx();
   BfsLane& ln = g_ring.lane[lane_id];
-  if (lane_id > 0 && !ln.d_rot) {
-    GRB_HIP_TRY(hipMalloc((void**)&ln.d_rot, 256));
-    GRB_HIP_TRY(hipMemset(ln.d_rot, 0, 256));
-  }
   if (lane_id > 0 && !co && !ln.stream) {
     GRB_HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
     GRB_HIP_TRY(hipEventCreateWithFlags(&ln.ev_in, hipEventDisableTiming));
     GRB_HIP_TRY(hipEventCreateWithFlags(&ln.ev_done, hipEventDisableTiming));
   }
   hipStream_t s = (lane_id > 0 && !co) ? ln.stream : c.stream;
-  unsigned int* d_rot = lane_id > 0 ? ln.d_rot : g_ring.d_rot;
   const Index n = A->nrows;
-  const int nwords = 2 * ceil_div(n, 64);
+  const LaneSizes z = lane_sizes(A, co);
+  const int nwords = z.nwords;
   int wgs_per_cu = 1;
   if (const char* e = getenv("GRB_BFS_WGS_PER_CU")) wgs_per_cu = atoi(e) >= 2 ? 2 : 1;
   static int max_per_cu = 0;
@@ -1465,20 +1561,18 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
   const int G = co ? c.num_cu * g_mult
                    : (g_ring.lanes > 1 && profile == 0 && g_ring.lanes_active) ? (c.num_cu / g_ring.lanes > 0 ? c.num_cu / g_ring.lanes : 1)
                                                                                : G_full;
-  const int rec_cap = 1 << 15;
-  const int big_cap = (int)(A->nvals / kBigDeg) + 2;
-
-  // one allocation: three blocks [state | V0 | F0 .. F(kKeep + 2)], used in rotation (PersistArgs::blocks)
-  const size_t st_bytes = (sizeof(PersistState) + 255) & ~(size_t)255;
-  const size_t block_bytes = (st_bytes + 4 * (size_t)(1 + kKeep + 3) * (size_t)nwords + 255) & ~(size_t)255;
-  const size_t zero_bytes = (co ? 3 : 2) * block_bytes;
+  const int rec_cap = z.rec_cap;
+  const int big_cap = z.big_cap;
+  const size_t st_bytes = z.st_bytes, block_bytes = z.block_bytes, zero_bytes = z.zero_bytes;
   void *p_zero, *p_v1, *p_big, *p_rec;
   int* p_blocksel = lane_id > 0 ? &ln.block : &g_ring.block;
+  if (lane_id > 0) GRB_TRY(lane_provide(lane_id, z, s));   // (a sub-grid's: in place already, co_provision)
+  unsigned int* d_rot = lane_id > 0 ? ln.d_rot : g_ring.d_rot;
   if (lane_id == 0) {
     GRB_TRY(scratch(7, zero_bytes, &p_zero));
-    GRB_TRY(scratch(8, 4 * (size_t)nwords, &p_v1));
-    GRB_TRY(scratch(2, sizeof(int2) * (size_t)big_cap, &p_big));
-    GRB_TRY(scratch(11, sizeof(grb_bfs_level) * (size_t)rec_cap, &p_rec));
+    GRB_TRY(scratch(8, z.v1_bytes, &p_v1));
+    GRB_TRY(scratch(2, z.big_bytes, &p_big));
+    GRB_TRY(scratch(11, z.rec_bytes, &p_rec));
     // every block is clear (and the rotation words say "nothing to clear") when somebody else has had the slot
     if (c.bfs_prezero_ptr != p_zero || c.bfs_prezero_bytes != zero_bytes) {
       GRB_HIP_TRY(hipMemsetAsync(p_zero, 0, zero_bytes, s));
@@ -1487,17 +1581,7 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
     }
     c.bfs_prezero_ptr = nullptr;
   } else {
-    const size_t had = ln.zero_cap;
-    GRB_TRY(lane_buffer(&ln.zero, &ln.zero_cap, zero_bytes, s));
-    GRB_TRY(lane_buffer(&ln.v1, &ln.v1_cap, 4 * (size_t)nwords, s));
-    GRB_TRY(lane_buffer(&ln.big, &ln.big_cap, sizeof(int2) * (size_t)big_cap, s));
-    GRB_TRY(lane_buffer(&ln.rec, &ln.rec_cap, sizeof(grb_bfs_level) * (size_t)rec_cap, s));
     p_zero = ln.zero; p_v1 = ln.v1; p_big = ln.big; p_rec = ln.rec;
-    if (had != ln.zero_cap || ln.clean_bytes != zero_bytes) {     // new memory, or a graph of another size: clear every block
-      GRB_HIP_TRY(hipMemsetAsync(p_zero, 0, zero_bytes, s));
-      GRB_HIP_TRY(hipMemsetAsync(d_rot, 0, 16, s));
-      ln.block = 0;
-    }
     ln.clean_bytes = 0;
   }
 
@@ -1566,7 +1650,6 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
     const char* e = getenv("GRB_BFS_OC_MIN");              // frontier out-edges from which a push level uses it; 0 = off
     const long long oc_min = e ? atoll(e) : 262144;
     const bool narrow = G != G_full || oc_words != kOcWords;   // a lane's grid, or narrower slices: its own tables (the ranges are cut per workgroup)
-    const int oc2_key = G + (oc_words << 12);
     if (!narrow) {
       if (oc_min > 0 && A->oc_state == 0) {
         A->oc_state = -1;
@@ -1585,21 +1668,7 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
         a.oc_min_edges = (unsigned long long)oc_min;
       }
     } else {
-      if (oc_min > 0 && (A->oc2_state == 0 || A->oc2_grid != oc2_key)) {
-        if (A->d_oc2_bounds || A->d_oc2_off || A->d_oc2_bigidx) {
-          GRB_HIP_TRY(hipDeviceSynchronize());               // (traversals of other lanes may be reading the old tables)
-          (void)hipFree(A->d_oc2_bounds); (void)hipFree(A->d_oc2_off); (void)hipFree(A->d_oc2_bigidx);
-          A->d_oc2_bounds = nullptr; A->d_oc2_off = nullptr; A->d_oc2_bigidx = nullptr;
-        }
-        A->oc2_state = -1;
-        A->oc2_grid = oc2_key;
-        if (A->nvals > 0 && (Index)A->h_csr_ptr.size() == n + 1) {
-          GRB_TRY(oc_tables_build(A->csr.ptr, A->csr.ind, A->h_csr_ptr, n, n, G, &A->d_oc2_bounds, &A->d_oc2_off, &A->d_oc2_bigidx,
-                                  &A->oc2_nb, &A->oc2_nrows, oc_words));
-          if (A->d_oc2_off) A->oc2_state = 1;
-          GRB_HIP_TRY(hipStreamSynchronize(c.stream));       // (built on the library's stream; the lanes read them)
-        }
-      }
+      if (oc_min > 0) GRB_TRY(oc2_tables_ensure(A, G, oc_words));
       if (oc_min > 0 && A->oc2_state == 1) {
         a.oc_bounds = A->d_oc2_bounds;
         a.oc_off = A->d_oc2_off;
@@ -1659,6 +1728,20 @@ void grb::bfs_lanes_unfence() {
   for (int l = 1; l <= kMaxLanes; ++l) g_ring.lane[l].fenced_epoch = ~0ull;
 }
 
+static int co_width_wanted(int width) { return width >= 1 && width < kCoMax ? width : kCoMax; }
+// What launches of several traversals of A need besides the matrix's own preparation -- the owner-computes tables cut
+// for the 128-thread sub-grids, every sub-grid's state -- made by A's first one-traversal launch while co-scheduling is
+// on, with the matrix's other once-per-matrix preparation (3.3 ms at RMAT-22: a caller's first blocking call or warm-up
+// pays it, not the first batch of queued traversals).  Nothing here is reported: what it could not make is made (or
+// found missing, and the launch narrowed) when a launch of several traversals needs it.
+static void co_prepare(grb_matrix A) {
+  if (g_ring.co_width == 1 || g_ring.lanes != 1) return;
+  const char* e = getenv("GRB_BFS_OC_MIN");
+  const bool narrow_slices = co_width_wanted(g_ring.co_width) > 4;      // (128-thread sub-grids: bfs_co_launch)
+  if (narrow_slices && (e ? atoll(e) : 262144) > 0 && oc2_tables_ensure(A, ctx().num_cu, kOcWords / 4) != GRB_SUCCESS) (void)hipGetLastError();
+  (void)co_provision(A, co_width_wanted(g_ring.co_width));
+}
+
 // Queues one traversal (on the library's stream, or on its lane's); its record will appear in ring slot `slot` under
 // tag *seq_out.
 static grb_info bfs_persistent_launch(grb_vector v, grb_matrix A, grb_index source, grb_descriptor desc, int profile, int slot,
@@ -1708,7 +1791,9 @@ static grb_info bfs_persistent_launch(grb_vector v, grb_matrix A, grb_index sour
     GRB_HIP_TRY(hipGetLastError());
   }
   if (profile & 1) GRB_HIP_TRY(hipEventRecord(c.ev1, s));
-  return bfs_persistent_queued(lc);
+  GRB_TRY(bfs_persistent_queued(lc));
+  if (lane_id == 0) co_prepare(A);
+  return GRB_SUCCESS;
 }
 
 // ntrav traversals (2 .. kCoTrain) of one matrix under one descriptor in ONE launch on the library's stream: n_grids
@@ -1723,13 +1808,22 @@ static grb_info co_kernel_fits(int k) {
   }
   return per_cu >= k ? GRB_SUCCESS : GRB_NOT_IMPLEMENTED;
 }
+// The width rule: sub-grids for a launch of ntrav traversals under the setting `width` (0: the library's choice) --
+// as many as there are traversals up to kCoMax, or the fixed number -- and never more than are provisioned.  (Spreading
+// the traversals evenly instead, ceil(ntrav / ceil(ntrav / kCoMax)) sub-grids -- 10 for 20, 11 for 32 -- so that no
+// sub-grid idles through the launch's last round, measured slower: docs/experiments.md R7.1.)
+static int co_grids(int ntrav, int width, int ready) {
+  int n = co_width_wanted(width);
+  if (n > ntrav) n = ntrav;
+  return n < ready ? n : ready;
+}
 static grb_info bfs_co_launch(int ntrav, const CoPend* pend, int width, int g_mult = 1) {
   Context& c = ctx();
   if (ntrav < (g_mult > 1 ? 1 : 2) || ntrav > kCoTrain) return GRB_INVALID_VALUE;
   static const bool force_fallback = [] { const char* e = getenv("GRB_BFS_FORCE_FALLBACK"); return e && atoi(e) != 0; }();
   if (force_fallback) return GRB_NOT_IMPLEMENTED;
-  int n_grids = width < ntrav ? width : ntrav;
-  if (n_grids > kCoMax) n_grids = kCoMax;
+  const int n_grids = co_grids(ntrav, width, co_provision(pend[0].A, co_width_wanted(width)));
+  if (n_grids < (g_mult > 1 ? 1 : 2)) return GRB_NOT_IMPLEMENTED;   // (no memory for a second sub-grid: one launch per traversal)
   // two sub-grids: 512-thread workgroups; three or four: 256; up to twelve: 128 (built for six waves per SIMD)
   const int T = n_grids <= 2 ? 512 : n_grids <= 4 ? 256 : 128;   // (a launch the CU cannot hold is refused: co_kernel_fits)
   GRB_TRY(T == 512 ? co_kernel_fits<512>(n_grids * g_mult) : T == 256 ? co_kernel_fits<256>(n_grids * g_mult) : co_kernel_fits<128>(n_grids * g_mult));
@@ -1868,14 +1962,18 @@ grb_info grb::bfs_persistent_enqueue(grb_vector v, grb_matrix A, grb_index sourc
   const auto t0 = std::chrono::steady_clock::now();
   GRB_TRY(ring_init());
   BfsTicket& t = g_ring.t[slot];
-  if (g_ring.co_width > 1 && g_ring.lanes == 1) {
-    // co-scheduling: the traversal gets its ticket now and its launch when somebody waits for a ticket, when any other
-    // entry point is called (bfs_co_flush), or when kCoTrain of them have gathered -- a launch runs co_width of them at a
-    // time and hands out the rest as its sub-grids come free, so the more it carries the less its tail weighs; the host
-    // queues a ticket in a microsecond, so gathering costs the device nothing it notices.  One launch serves one matrix
-    // and one set of descriptor fields.
+  if (g_ring.co_width != 1 && g_ring.lanes == 1) {
+    // co-scheduling (the default): the traversal gets its ticket now and its launch when somebody waits for a ticket, when
+    // any other entry point is called (bfs_co_flush), or when kCoTrain of them have gathered -- a launch runs up to kCoMax
+    // of them at a time and hands out the rest as its sub-grids come free, so the more it carries the less its tail
+    // weighs; the host queues a ticket in a microsecond, so gathering costs the device nothing it notices.  One launch
+    // serves one matrix and one set of descriptor fields, and writes a vector once: the traversals of a launch run
+    // concurrently, so a second one into the same vector goes to the next launch, which the stream orders behind it
+    // (the last one queued into a vector wins, as with one launch per traversal).
     const BfsRules rules = bfs_rules_of(desc);
-    if (g_ring.co_n > 0 && (g_ring.co[0].A != A || !(g_ring.co[0].rules == rules))) GRB_TRY(bfs_co_flush());
+    bool flush = g_ring.co_n > 0 && (g_ring.co[0].A != A || !(g_ring.co[0].rules == rules));
+    for (int j = 0; j < g_ring.co_n && !flush; ++j) flush = g_ring.co[j].v == v;
+    if (flush) GRB_TRY(bfs_co_flush());
     *seq = ++ctx().mail_seq;
     CoPend& p = g_ring.co[g_ring.co_n++];
     p.slot = slot; p.seq = *seq; p.v = v; p.A = A; p.source = source; p.desc = desc; p.rules = rules;
@@ -1960,10 +2058,11 @@ grb_info grb::bfs_co_profile(int on, double* ms_total, int* launches, int* trave
   g_ring.co_prof_trav = 0;
   return GRB_SUCCESS;
 }
-// Traversals per launch (1 .. kCoMax).  Everything queued so far is launched and waited for first.  Returns the previous value.
+// Traversals per launch (1 .. kCoMax).  Everything queued so far is launched and waited for first.  Returns the previous
+// value; 1 while the width rule picks it (the default, which no call restores: set_coschedule(1) fixes one per launch).
 int grb::bfs_co_setting(int set) {
-  const int before = g_ring.co_width;
-  if (set >= 1 && set != before) {
+  const int before = g_ring.co_width >= 1 ? g_ring.co_width : 1;
+  if (set >= 1 && set != g_ring.co_width) {
     (void)bfs_co_flush();
     (void)hipDeviceSynchronize();
     g_ring.co_width = set > kCoMax ? kCoMax : set;

@@ -320,9 +320,12 @@ grb_info grb_bfs_fused(grb_vector v, grb_matrix A, grb_index source, grb_descrip
 /* The same traversal, queued without waiting: the launch is put on the library's stream and the call returns; the
  * result block is read by grb_bfs_wait.  K traversals into K vectors run back to back on the device with no host
  * round trip between them (the reference's loop returns to the host several times per LEVEL, algorithm/bfs.hpp:42-88:
- * `reduce` -> succ, `nvals`, the timing branches).  Traversals execute in the order they were queued; v, A and desc must
- * stay alive and untouched by the caller until the ticket has been waited for (v's contents are undefined until then;
- * any other entry point may be called meanwhile -- it is ordered behind the queued traversals on the stream).  At most
+ * `reduce` -> succ, `nvals`, the timing branches).  The results are as if the traversals ran in the order they were
+ * queued (several may run side by side in one launch, grb_bfs_set_coschedule: never two into the same vector); v, A and
+ * desc must stay alive and untouched by the caller until the ticket has been waited for (v's contents are undefined
+ * until then; any other entry point may be called meanwhile -- it is ordered behind the queued traversals on the
+ * stream).  Under co-scheduling (the default) a queued traversal starts on the device when a ticket is waited for or
+ * another entry point is called, not at the enqueue (see grb_bfs_set_coschedule).  At most
  * 256 tickets may be outstanding (GRB_INSUFFICIENT_SPACE).  A traversal the one-launch kernel does not serve (road-network
  * queues, GRB_SPARSE_MATRIX_FORMAT=1) runs to its end inside the enqueue call; its ticket waits like any other.
  * grb_bfs_wait returns what grb_bfs_fused would have returned (a launch that could not finish is re-run through the
@@ -343,7 +346,13 @@ grb_info grb_bfs_wait(grb_bfs_ticket ticket, grb_bfs_result* result);
  * blocking grb_bfs_fused keeps the whole device (and, issued while lanes are busy, waits for their grids to drain).
  * Changing the number waits for everything queued.  n < 1 only queries.  Returns the previous value. */
 int grb_bfs_set_lanes(int n);
-/* Traversals side by side in one LAUNCH (1 .. 12; default 1).  With k > 1 the traversals queued by grb_bfs_fused_enqueue
+/* Traversals side by side in one LAUNCH (1 .. 12).  By default the library co-schedules by itself: a launch has one
+ * sub-grid per gathered traversal, up to twelve, as many as fit in a quarter of the device memory that is free (a
+ * sub-grid keeps about 77 MB of state at RMAT-22, provisioned with the matrix's once-per-matrix preparation by its first
+ * one-traversal launch, or else by the first launch of several; when memory runs short the launches narrow, down to one
+ * traversal per launch), and a lone gathered traversal takes the
+ * one-traversal kernel.  k = 1 gives every traversal its own launch at the enqueue; k > 1 fixes k.  With co-scheduling
+ * the traversals queued by grb_bfs_fused_enqueue
  * share launches: a launch is k sub-grids of one workgroup per CU each (512 threads for two, 256 up to four, 128 up to
  * twelve -- that instance is built for six waves per SIMD), every sub-grid runs one traversal at a time on state,
  * barrier counters and bitmaps of its own, and when it has finished one it draws the next of the launch's traversals (up to 48 per launch) from a counter.  A traversal is
@@ -351,12 +360,14 @@ int grb_bfs_set_lanes(int n);
  * traversals' work, and -- unlike lanes -- nothing depends on how the runtime maps streams to hardware queues: it is one
  * launch on the library's stream.  A ticket is issued at once; the launch goes out when one of the gathered tickets is
  * waited for, when any other entry point is called (so the ordering rules of grb_bfs_fused_enqueue hold unchanged),
- * when a traversal of another matrix or descriptor is queued, or when 48 have gathered.  Per-traversal labels and
+ * when a traversal of another matrix or descriptor, or one into a vector a gathered one writes, is queued, or when 48
+ * have gathered.  Per-traversal labels and
  * result blocks are those of grb_bfs_fused; a traversal's record is written after a barrier of its sub-grid, i.e. when
  * every label store has completed.  A traversal runs under the descriptor fields (mxvmode, switchpoint, edgeswitch,
  * max_niter) as they stood when it was QUEUED -- the descriptor's setters launch nothing, and one launch serves one set of
  * rules (a traversal queued under other rules starts a new launch).  Ignored while grb_bfs_set_lanes is above 1.  Changing the number launches and waits
- * for everything queued.  k < 1 only queries.  Returns the previous value.  (No counterpart in the reference, whose loop
+ * for everything queued.  k < 1 only queries.  Returns the previous value: the k last set, 1 while the library chooses
+ * (a caller who restores what a query returned gets one traversal per launch).  (No counterpart in the reference, whose loop
  * is one traversal with several host round trips per level: algorithm/bfs.hpp:42-88.) */
 int grb_bfs_set_coschedule(int k);
 /* Measurement: HIP events on the library's stream around every launch of several traversals.  on != 0 starts collecting
