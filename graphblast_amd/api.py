@@ -428,6 +428,11 @@ def apply(w, mask, accum, unary, u, desc, binop=None, scalar=0.0):
 
 
 def mxm(Cm, mask, accum, op, A, B, desc):
+    """graphblas::mxm: C = op(A) (+.x) op(B) (GrB_INP0 / GrB_INP1 = GrB_TRAN transpose an operand).  With a mask, C takes
+    the mask's structure.  With mask=None, the unmasked product: float32 A, B and C only (GrB_NOT_IMPLEMENTED otherwise),
+    any semiring, products folded over k ascending; C == A or B -> GrB_NOT_IMPLEMENTED, shapes -> GrB_DIMENSION_MISMATCH,
+    a transposed operand without its CSC -> GrB_INVALID_OBJECT, more than INT32_MAX results -> GrB_OUT_OF_MEMORY (C
+    unchanged).  Returns the info code."""
     return _lib.load().grb_mxm(_h(Cm), _h(mask), _accum(accum), _semiring_id(op), _h(A), _h(B), _h(desc))
 
 

@@ -310,6 +310,15 @@ __global__ void rank_scatter_kernel(const unsigned long long* __restrict__ keys,
 
 using namespace grb;
 
+// The same scan with the tile totals in a buffer of the caller's (device_scan_u32_scratch(n) bytes); synchronises.
+size_t grb::device_scan_u32_scratch(long long n) { return 4 * (size_t)((n > 0 ? n : 0) / kScanTile + 2); }
+grb_info grb::device_exclusive_scan_u32_in(unsigned int* d, long long n, unsigned int* totals) {
+  if (n <= 0) return GRB_SUCCESS;
+  GRB_TRY(exclusive_scan_u32(d, n, totals, ctx().stream));
+  GRB_HIP_TRY(hipStreamSynchronize(ctx().stream));
+  return GRB_SUCCESS;
+}
+
 // In-place exclusive scan of n unsigned ints on the context stream (scratch for the tile totals allocated here).
 grb_info grb::device_exclusive_scan_u32(unsigned int* d, long long n) {
   if (n <= 0) return GRB_SUCCESS;

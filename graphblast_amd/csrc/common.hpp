@@ -774,6 +774,8 @@ void free_spmv_plan(SpmvPlan* plan);
 // build.hip: columns ranked by descending reference count on the device (d_other_ptr: the transposed
 // orientation's pointer array, whose differences ARE the counts; nullptr: histogram of d_ind)
 grb_info device_exclusive_scan_u32(unsigned int* d, long long n);   // build.hip
+size_t device_scan_u32_scratch(long long n);                        // bytes of tile totals the scan below needs
+grb_info device_exclusive_scan_u32_in(unsigned int* d, long long n, unsigned int* totals);   // ... in a buffer of the caller's
 grb_info device_sort_pairs(unsigned long long* d_keys, unsigned int* d_pay, long long n, int lo_bits, int hi_bits);   // build.hip
 grb_info device_sort_pairs_range(unsigned long long* d_keys, unsigned int* d_pay, long long n, int first_bit, int nbits);
 grb_info device_rank_columns(const Index* d_ind, Index nvals, const Index* d_other_ptr, Index m, Index hot,
@@ -851,6 +853,9 @@ void bfs_lanes_unfence();                        // the lanes' next launches wai
 grb_info k_spmv_masked_or(int dtype, const CsrArrays& M, const void* u, double identity,
                           const void* mask, int mask_f32, int scmp, int earlyexit, int opreuse,
                           const Index* hint /* per-row best neighbour, may be null */, void* w);
+
+// spgemm.hip: C = op(A) (+.x) op(B) without a mask (grb_mxm with a null mask); f32 only, GRB_NOT_IMPLEMENTED otherwise
+grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool tran_a, bool tran_b);
 
 // spmspv.hip
 grb_info k_spmspv(int sr, int dtype, const CsrArrays& M, Index out_size, int struconly,

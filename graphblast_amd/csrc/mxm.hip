@@ -1102,7 +1102,8 @@ grb_info grb_mxm(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op
   (void)accum;
   if (!C || !A || !B || !desc) return GRB_UNINITIALIZED_OBJECT;
   if (!A->built || !B->built) return GRB_UNINITIALIZED_OBJECT;
-  if (!mask) return GRB_NOT_IMPLEMENTED;                 // unmasked SpGEMM is a cuSPARSE call in the reference
+  if (!mask)                                             // unmasked: f32 only, as the reference's cuSPARSE call (spgemm.hip)
+    return spgemm_unmasked(C, op, A, B, desc->desc[GRB_INP0] == GRB_TRAN, desc->desc[GRB_INP1] == GRB_TRAN);
   if (!mask->built) return GRB_UNINITIALIZED_OBJECT;
   if (C == A || C == B || C == mask) return GRB_NOT_IMPLEMENTED;
   if (A->dtype != B->dtype || C->dtype != A->dtype) return GRB_DOMAIN_MISMATCH;

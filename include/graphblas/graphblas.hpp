@@ -988,7 +988,8 @@ Info apply(Vector<W>* w, const Vector<M>* mask, BinaryOpT accum, UnaryOpT op, co
   return w->build(&wv, un);
 }
 
-// mxm: masked SpGEMM only (operations.hpp:22-48; unmasked is a cuSPARSE call in the reference)
+// mxm (operations.hpp:22-48): masked SpGEMM, or with mask == GrB_NULL the unmasked product for float matrices (a cuSPARSE
+// call in the reference; here every semiring is honoured); other types without a mask are GrB_NOT_IMPLEMENTED
 template <typename c, typename m, typename a, typename b, typename BinaryOpT, typename SemiringT>
 Info mxm(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT op, const Matrix<a>* A, const Matrix<b>* B,
          Descriptor* desc) {

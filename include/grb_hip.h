@@ -266,7 +266,16 @@ grb_info grb_vector_apply(grb_vector w, grb_vector mask, grb_accum accum, int un
 grb_info grb_matrix_apply(grb_matrix C, grb_matrix mask, grb_accum accum, int unary, int binop, double scalar, grb_matrix A,
                           grb_descriptor desc);
 
-/* mxm, masked SpGEMM only   operations.hpp:22-48 -> backend :18-78 (spgemm.hpp:22-110) */
+/* mxm   operations.hpp:22-51 -> backend :18-78.  C = op(A) (+.x) op(B); op(A) is A^T under GrB_INP0 = GrB_TRAN (read from
+ * A's CSC), op(B) is B^T under GrB_INP1 = GrB_TRAN (read from B's CSC); accum and the other descriptor fields are ignored.
+ * With a mask (spgemm.hpp:22-110): C takes the mask's structure and C(i,j) is computed where the mask value is nonzero.
+ * Without one (mask == NULL; the reference's cuSPARSE call, spgemm.hpp:282-): f32 A, B and C only -- every other type
+ * combination is GRB_NOT_IMPLEMENTED, as in the reference -- but every semiring is honoured, registered ones included.
+ * C holds every (i, j) with at least one k where op(A)(i,k) and op(B)(k,j) are both stored (stored zeros count), columns
+ * ascending, C(i,j) = add(mul(a_ik, b_kj), acc) folded over k ascending from the identity; the same inputs give the same
+ * bits.  C == A or C == B: GRB_NOT_IMPLEMENTED; the side an orientation needs absent: GRB_INVALID_OBJECT; inner or outer
+ * dimensions that do not agree: GRB_DIMENSION_MISMATCH; more than INT32_MAX entries in C, or a failed device allocation:
+ * GRB_OUT_OF_MEMORY.  On any error C keeps what it held.  The result is CSR only (no CSC), as the masked product's. */
 grb_info grb_mxm(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op, grb_matrix A, grb_matrix B,
                  grb_descriptor desc);
 /* eWiseMult, matrix (x) broadcast scalar / vector, in place (C == A)   operations.hpp:206-267 ->
