@@ -385,11 +385,23 @@ def mxv(w, mask, accum, op, A, u, desc):
 
 
 def eWiseMult(w, mask, accum, op, u, v, desc):
+    """eWiseMult(w, mask, accum, op, u, v, desc) on vectors, or with u a Matrix the matrix form (see eWiseAdd): C = op(A) (x)
+    op(B) on the intersection of the two structures, C(i,j) = mul(a, b)."""
+    if isinstance(u, Matrix) or isinstance(w, Matrix):
+        return _lib.load().grb_matrix_eWiseMult(_h(w), _h(mask), _accum(accum), _semiring_id(op), _h(u), _h(v), _h(desc))
     return _lib.load().grb_eWiseMult(_h(w), _h(mask), _accum(accum), _semiring_id(op), _h(u), _h(v), _h(desc))
 
 
 def eWiseAdd(w, mask, accum, op, u, v, desc):
-    """eWiseAdd(w, mask, accum, op, u, v | scalar, desc)."""
+    """eWiseAdd(w, mask, accum, op, u, v | scalar, desc).  With u a Matrix: C = op(A) (+) op(B) (GrB_INP0 / GrB_INP1 =
+    GrB_TRAN transpose an operand, read from its CSC) on the union of the two structures, C(i,j) = add(a, b) where both
+    store an entry and the stored value where one does; stored zeros are kept.  A mask keeps the entries where it stores a
+    nonzero (inverted by GrB_SCMP).  f32 or i32, all three alike (GrB_NOT_IMPLEMENTED otherwise); C may be A, B or the
+    mask; shapes -> GrB_DIMENSION_MISMATCH, a transposed operand without its CSC -> GrB_INVALID_OBJECT, more than INT32_MAX
+    entries -> GrB_OUT_OF_MEMORY (C unchanged on every error).  C gets a CSC too when every input has its other
+    orientation.  Returns the info code."""
+    if isinstance(u, Matrix) or isinstance(w, Matrix):
+        return _lib.load().grb_matrix_eWiseAdd(_h(w), _h(mask), _accum(accum), _semiring_id(op), _h(u), _h(v), _h(desc))
     if isinstance(v, Vector):
         return _lib.load().grb_eWiseAdd(_h(w), _h(mask), _accum(accum), _semiring_id(op), _h(u), _h(v), _h(desc))
     return _lib.load().grb_eWiseAdd_scalar(_h(w), _h(mask), _accum(accum), _semiring_id(op), _h(u), float(v),
@@ -434,6 +446,13 @@ def mxm(Cm, mask, accum, op, A, B, desc):
     a transposed operand without its CSC -> GrB_INVALID_OBJECT, more than INT32_MAX results -> GrB_OUT_OF_MEMORY (C
     unchanged).  Returns the info code."""
     return _lib.load().grb_mxm(_h(Cm), _h(mask), _accum(accum), _semiring_id(op), _h(A), _h(B), _h(desc))
+
+
+def transpose(Cm, mask, accum, A, desc):
+    """graphblas::transpose: C = A^T, or C = A under GrB_INP0 = GrB_TRAN, with both orientations (a CSR-only A, such as a
+    product result, is sorted on the device).  f32 or i32, C of A's type; a mask -> GrB_NOT_IMPLEMENTED; C may be A; C
+    unchanged on every error.  Returns the info code."""
+    return _lib.load().grb_transpose(_h(Cm), _h(mask), _accum(accum), _h(A), _h(desc))
 
 
 def tril(Cm, A, desc):

@@ -856,6 +856,13 @@ grb_info k_spmv_masked_or(int dtype, const CsrArrays& M, const void* u, double i
 
 // spgemm.hip: C = op(A) (+.x) op(B) without a mask (grb_mxm with a null mask); f32 only, GRB_NOT_IMPLEMENTED otherwise
 grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool tran_a, bool tran_b);
+// ewise_matrix.hip: C<mask> = op(A) (+) op(B) (add: the union) or op(A) (x) op(B) (the intersection), f32 or i32; and
+// C = A^T (tran = false) or A (tran = true) with both orientations.  C may be A, B or the mask; C keeps what it held on error
+grb_info ewise_matrix(grb_matrix C, grb_matrix mask, int op, grb_matrix A, grb_matrix B, bool tran_a, bool tran_b, bool scmp,
+                      bool add);
+grb_info transpose_matrix(grb_matrix C, grb_matrix A, bool tran);
+// objects.hip: the CSR-only format's aliasing of a built matrix (GRB_SPARSE_MATRIX_FORMAT = 1; nothing otherwise)
+grb_info matrix_apply_format(grb_matrix A);
 
 // spmspv.hip
 grb_info k_spmspv(int sr, int dtype, const CsrArrays& M, Index out_size, int struconly,

@@ -1434,6 +1434,35 @@ grb_info grb_matrix_eWiseMult_vector(grb_matrix C, grb_semiring op, grb_matrix A
   return matrix_scale(A, op, B, 0.0, desc->desc[GRB_INP1] != GRB_TRAN);
 }
 
+// eWiseAdd / eWiseMult of two matrices (operations.hpp:166-204, 307-325) and transpose (operations.hpp:682): ewise_matrix.hip
+static grb_info ewise_entry(grb_matrix C, grb_matrix mask, grb_semiring op, grb_matrix A, grb_matrix B, grb_descriptor desc,
+                            bool add) {
+  if (!C || !A || !B || !desc) return GRB_UNINITIALIZED_OBJECT;
+  if (!A->built || !B->built || (mask && !mask->built)) return GRB_UNINITIALIZED_OBJECT;
+  return ewise_matrix(C, mask, op, A, B, desc->desc[GRB_INP0] == GRB_TRAN, desc->desc[GRB_INP1] == GRB_TRAN,
+                      mask && desc->desc[GRB_MASK] == GRB_SCMP, add);
+}
+
+grb_info grb_matrix_eWiseAdd(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op, grb_matrix A, grb_matrix B,
+                             grb_descriptor desc) { GRB_API_ENTER();
+  (void)accum;
+  return ewise_entry(C, mask, op, A, B, desc, true);
+}
+
+grb_info grb_matrix_eWiseMult(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op, grb_matrix A, grb_matrix B,
+                              grb_descriptor desc) { GRB_API_ENTER();
+  (void)accum;
+  return ewise_entry(C, mask, op, A, B, desc, false);
+}
+
+grb_info grb_transpose(grb_matrix C, grb_matrix mask, grb_accum accum, grb_matrix A, grb_descriptor desc) { GRB_API_ENTER();
+  (void)accum;
+  if (!C || !A || !desc) return GRB_UNINITIALIZED_OBJECT;
+  if (!A->built || (mask && !mask->built)) return GRB_UNINITIALIZED_OBJECT;
+  if (mask) return GRB_NOT_IMPLEMENTED;
+  return transpose_matrix(C, A, desc->desc[GRB_INP0] == GRB_TRAN);
+}
+
 grb_info grb_reduce_matrix_scalar(double* val, grb_accum accum, grb_monoid op, grb_matrix A, grb_descriptor desc) { GRB_API_ENTER();
   (void)accum;
   if (!val || !A || !desc) return GRB_UNINITIALIZED_OBJECT;

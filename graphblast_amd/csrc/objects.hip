@@ -914,6 +914,8 @@ static grb_info apply_format(grb_matrix A) {
   return build_spmv_plan(A->h_csr_ptr, A->nrows, A->ncols, &A->plan_csc);
 }
 
+extern "C++" grb_info grb::matrix_apply_format(grb_matrix A) { return apply_format(A); }
+
 static grb_info matrix_finish_build(grb_matrix A) {
   A->owned = true;
   GRB_TRY(upload(&A->csr, A->nrows, A->nvals, A->h_csr_ptr, A->h_csr_ind, A->h_csr_val));

@@ -1044,10 +1044,13 @@ Info apply(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, UnaryOpT op, co
   return C->transform_values([&](Index, Index, c v) { return op(v); });
 }
 
-// eWiseMult, matrix x broadcast scalar (operations.hpp:206-228; example/gpr.cu:82-84)
+// eWiseMult, matrix x broadcast scalar (operations.hpp:206-228; example/gpr.cu:82-84).  Only for an arithmetic `val`: a
+// Matrix* or Vector* operand takes the overloads below even when its pointer is not const (an identity match on `b`
+// would otherwise beat their qualification conversion)
 template <typename c, typename m, typename a, typename b, typename BinaryOpT, typename SemiringT>
-Info eWiseMult(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT op, const Matrix<a>* A, b val,
-               Descriptor* desc) {
+typename std::enable_if<std::is_arithmetic<b>::value, Info>::type
+eWiseMult(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT op, const Matrix<a>* A, b val,
+          Descriptor* desc) {
   if (C == NULL || A == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
   if (mask != NULL || static_cast<const void*>(C) != static_cast<const void*>(A)) return GrB_NOT_IMPLEMENTED;
   (void)accum;
@@ -1083,6 +1086,48 @@ Info eWiseMult(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT o
   if (i != GrB_SUCCESS) return i;
   const bool by_col = (inp1 == GrB_TRAN);
   return C->transform_values([&](Index r, Index col, c v) { return op.mul_op(v, static_cast<c>(bv[by_col ? col : r])); });
+}
+
+// eWiseAdd / eWiseMult of two matrices (operations.hpp:166-204, 307-325; not implemented by the reference's backend):
+// C<mask> = op(A) (+) op(B) on the union of the structures, or op(A) (x) op(B) on their intersection (grb_hip.h)
+namespace detail {
+template <typename c>
+inline Info refresh_result(Matrix<c>* C) {     // C has a CSC when every input had its other orientation
+  if (grb_matrix_host_csc(C->handle(), NULL, NULL, NULL) == GRB_SUCCESS) return C->refresh_all();
+  C->refresh_csr_only();
+  return GrB_SUCCESS;
+}
+}  // namespace detail
+
+template <typename c, typename m, typename a, typename b, typename BinaryOpT, typename SemiringT>
+Info eWiseAdd(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT op, const Matrix<a>* A, const Matrix<b>* B,
+              Descriptor* desc) {
+  if (C == NULL || A == NULL || B == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  Info i = to_info(grb_matrix_eWiseAdd(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), detail::accum_of(accum),
+                                       detail::sr_id<SemiringT>(), A->handle(), B->handle(), desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
+template <typename c, typename m, typename a, typename b, typename BinaryOpT, typename SemiringT>
+Info eWiseMult(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT op, const Matrix<a>* A, const Matrix<b>* B,
+               Descriptor* desc) {
+  if (C == NULL || A == NULL || B == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  Info i = to_info(grb_matrix_eWiseMult(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), detail::accum_of(accum),
+                                        detail::sr_id<SemiringT>(), A->handle(), B->handle(), desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
+// transpose (operations.hpp:682): C = A^T, or C = A with GrB_INP0 = GrB_TRAN, with both orientations; a mask is
+// GrB_NOT_IMPLEMENTED
+template <typename c, typename m, typename a, typename BinaryOpT>
+Info transpose(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, const Matrix<a>* A, Descriptor* desc) {
+  if (C == NULL || A == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  Info i = to_info(grb_transpose(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), detail::accum_of(accum),
+                                 A->handle(), desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
 }
 
 #undef GRB_H

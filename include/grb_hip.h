@@ -284,6 +284,30 @@ grb_info grb_mxm(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op
 grb_info grb_matrix_eWiseMult_scalar(grb_matrix C, grb_semiring op, grb_matrix A, double val);
 grb_info grb_matrix_eWiseMult_vector(grb_matrix C, grb_semiring op, grb_matrix A, grb_vector B,
                                      grb_descriptor desc);
+/* eWiseAdd / eWiseMult of two matrices   operations.hpp:166-204 (eWiseMult), 307-325 (eWiseAdd); the reference's
+ * backend returns GrB_NOT_IMPLEMENTED (backend/cuda/operations.hpp:414-423).  op(A) is A^T under GrB_INP0 = GrB_TRAN and
+ * op(B) is B^T under GrB_INP1 = GrB_TRAN, read from that matrix's CSC as grb_mxm reads it (eWiseAdd(C, A, A) with INP1 =
+ * TRAN is A + A^T).  C holds the union (eWiseAdd) or the intersection (eWiseMult) of the two structures -- stored zeros
+ * count, nothing is dropped by value -- with columns ascending in every row.  An entry in both: add(a, b) (eWiseAdd) or
+ * mul(a, b) (eWiseMult) of op's operators, a from op(A) first; an entry in one operand only (eWiseAdd): copied bit for
+ * bit.  The same inputs give the same bits.  With a mask, an entry is kept only where the mask stores a nonzero value
+ * (mxm's rule), inverted under GrB_MASK = GrB_SCMP; the mask is f32 or i32 and read from its CSR.  accum and the other
+ * descriptor fields are ignored: C is replaced, as grb_mxm replaces it.  A, B and C all GRB_F32 or all GRB_I32, else
+ * GRB_NOT_IMPLEMENTED.  C may be A, B or the mask.  On any error C keeps what it held: a null handle or an unbuilt A, B or
+ * mask: GRB_UNINITIALIZED_OBJECT; shapes of op(A), op(B), C and the mask that differ: GRB_DIMENSION_MISMATCH; a transposed
+ * operand without a CSC of its own (a product result, the CSR-only format): GRB_INVALID_OBJECT; more than INT32_MAX
+ * entries in C, or a failed device allocation: GRB_OUT_OF_MEMORY.  C always gets its CSR, and also a CSC (the same merge
+ * over the other orientations: the same entries and bits) when op(A), op(B) and the mask each have their other
+ * orientation; otherwise C is CSR only, as a product result.  A C of the CSR-only format aliases its CSC to the CSR. */
+grb_info grb_matrix_eWiseAdd(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op, grb_matrix A, grb_matrix B,
+                             grb_descriptor desc);
+grb_info grb_matrix_eWiseMult(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op, grb_matrix A, grb_matrix B,
+                              grb_descriptor desc);
+/* transpose   operations.hpp:682.  C = A^T, or C = A under GrB_INP0 = GrB_TRAN (GraphBLAS's definition), f32 or i32 with
+ * C of A's type (else GRB_NOT_IMPLEMENTED); a mask: GRB_NOT_IMPLEMENTED.  C gets both orientations, sorted (subject to
+ * its own format): two device copies when A has both, a device sort of A's CSR when A is CSR only.  So transpose with
+ * INP0 = TRAN is how a product result gets a CSC.  Aliasing, error codes and C after an error as for eWiseAdd. */
+grb_info grb_transpose(grb_matrix C, grb_matrix mask, grb_accum accum, grb_matrix A, grb_descriptor desc);
 /* reduce (matrix -> scalar)   operations.hpp:662-680 -> backend :1032-1059 (reduce.hpp:81-91) */
 grb_info grb_reduce_matrix_scalar(double* val, grb_accum accum, grb_monoid op, grb_matrix A, grb_descriptor desc);
 /* traceMxmTranspose (extension)   operations.hpp:698-711 -> backend :1076-1108 (trace.hpp:10-52):
