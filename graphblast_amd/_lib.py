@@ -109,6 +109,9 @@ _SIGS = {
     "grb_matrix_eWiseAdd": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "grb_matrix_eWiseMult": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "grb_transpose": [_vp, _vp, _i, _vp, _vp],
+    "grb_matrix_extract": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp],
+    "grb_matrix_extract_col": [_vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "grb_vector_extract": [_vp, _vp, _i, _vp, _vp, _i, _vp],
     "grb_matrix_nrows": [_vp, _ip],
     "grb_matrix_ncols": [_vp, _ip],
     "grb_matrix_nvals": [_vp, _ip],

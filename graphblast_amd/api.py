@@ -455,6 +455,44 @@ def transpose(Cm, mask, accum, A, desc):
     return _lib.load().grb_transpose(_h(Cm), _h(mask), _accum(accum), _h(A), _h(desc))
 
 
+def _index_list(indices, dim):
+    """None (GrB_ALL) -> (None, dim); anything else -> a contiguous int32 array and its length"""
+    if indices is None:
+        return None, int(dim)
+    a = np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1))
+    return a, a.size
+
+
+def extract(out, mask, accum, src, rows, cols, desc):
+    """graphblas::extract, the three forms by the types of out and src; rows / cols are None (GrB_ALL: every index in
+    order) or anything np.asarray(..., np.int32) takes, in any order, duplicates allowed (a duplicate repeats a row, a
+    column or an element).  GrB_INP0 = GrB_TRAN reads A^T (from A's CSC; for the column form: row `cols` of A).
+    Matrix, Matrix: C = op(A)(rows, cols), C(i, j) = op(A)(rows[i], cols[j]) where stored (stored zeros kept, values
+    copied bit for bit, columns ascending); f32 or i32, C of A's type; C may be A; C gets a CSC too when op(A) has its other
+    orientation.  Vector, Matrix: w = op(A)(rows, cols) with cols an int: a sparse w of size len(rows).  Vector, Vector
+    (cols must be None): w = u(rows), dense for a dense u and sparse for a sparse one; w may be u.  A mask ->
+    GrB_NOT_IMPLEMENTED; shapes that differ from the lists' lengths -> GrB_DIMENSION_MISMATCH; an index outside op(A) / u ->
+    GrB_INDEX_OUT_OF_BOUNDS; a transposed operand without its CSC -> GrB_INVALID_OBJECT; more than INT32_MAX entries ->
+    GrB_OUT_OF_MEMORY (the output unchanged on every error).  Returns the info code."""
+    lib = _lib.load()
+    ptr = lambda a: None if a is None else a.ctypes.data
+    tran = desc is not None and desc.get(GrB_INP0) == GrB_TRAN
+    if isinstance(out, Matrix):
+        m, n = (0, 0) if src is None else (src.ncols(), src.nrows()) if tran else (src.nrows(), src.ncols())
+        r, nr = _index_list(rows, m)
+        c, nc = _index_list(cols, n)
+        return lib.grb_matrix_extract(_h(out), _h(mask), _accum(accum), _h(src), ptr(r), nr, ptr(c), nc, _h(desc))
+    if isinstance(src, Matrix):
+        r, nr = _index_list(rows, src.ncols() if tran else src.nrows())
+        if not isinstance(cols, (int, np.integer)):
+            raise TypeError("extract(Vector, Matrix): cols is the column's index")
+        return lib.grb_matrix_extract_col(_h(out), _h(mask), _accum(accum), _h(src), ptr(r), nr, int(cols), _h(desc))
+    if cols is not None:
+        raise TypeError("extract(Vector, Vector): cols must be None")
+    r, nr = _index_list(rows, src.size() if src is not None else 0)
+    return lib.grb_vector_extract(_h(out), _h(mask), _accum(accum), _h(src), ptr(r), nr, _h(desc))
+
+
 def tril(Cm, A, desc):
     return _lib.load().grb_matrix_tril(_h(Cm), _h(A), _h(desc))
 

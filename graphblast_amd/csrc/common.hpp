@@ -861,6 +861,30 @@ grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool 
 grb_info ewise_matrix(grb_matrix C, grb_matrix mask, int op, grb_matrix A, grb_matrix B, bool tran_a, bool tran_b, bool scmp,
                       bool add);
 grb_info transpose_matrix(grb_matrix C, grb_matrix A, bool tran);
+// ... and how such a result is installed in C (ewise_matrix.hip; extract.hip does the same).  Device memory of one call,
+// freed on the way out unless released to C:
+struct EwmBuf {
+  void* p = nullptr;
+  EwmBuf() = default;
+  EwmBuf(const EwmBuf&) = delete;
+  ~EwmBuf() { if (p) (void)hipFree(p); }
+  void* release() { void* q = p; p = nullptr; return q; }
+};
+grb_info ewm_alloc(EwmBuf* b, size_t bytes);   // GRB_OUT_OF_MEMORY when the device has no room
+// one orientation of a result: device arrays and the host copy of the pointers
+struct Side {
+  EwmBuf ptr, ind, val;
+  std::vector<Index> h_ptr;
+  Index nnz = 0;
+};
+// an orientation is usable when it is there and is not the CSR-only format's alias of the CSR
+bool has_csc(const grb_matrix_s* X);
+// C is replaced by r (its CSR) and c (its CSC, nullable); an input that is C is read before this
+grb_info attach(grb_matrix C, Side* r, Side* c);
+// extract.hip: C = op(A)(I, J), w = op(A)(I, j), w = u(I) (grb_hip.h: the three extract forms); null lists: all, in order
+grb_info extract_matrix(grb_matrix C, grb_matrix A, const Index* rows, Index nrows, const Index* cols, Index ncols, bool tran);
+grb_info extract_matrix_col(grb_vector w, grb_matrix A, const Index* rows, Index nrows, Index col, bool tran);
+grb_info extract_vector(grb_vector w, grb_vector u, const Index* indices, Index nindices);
 // objects.hip: the CSR-only format's aliasing of a built matrix (GRB_SPARSE_MATRIX_FORMAT = 1; nothing otherwise)
 grb_info matrix_apply_format(grb_matrix A);
 

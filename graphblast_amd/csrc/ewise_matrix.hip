@@ -273,16 +273,8 @@ __global__ __launch_bounds__(kBlock) void ewm_tr_ptr_kernel(const unsigned long 
   }
 }
 
-namespace {
-// device memory of one call: freed on the way out unless released to C
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  void* release() { void* q = p; p = nullptr; return q; }
-};
-grb_info ewm_alloc(DevBuf* b, size_t bytes) {
+// (EwmBuf, Side: common.hpp -- extract.hip installs its results the same way)
+grb_info ewm_alloc(EwmBuf* b, size_t bytes) {
   if (hipMalloc(&b->p, bytes ? bytes : 4) != hipSuccess) {
     (void)hipGetLastError();                             // (the failed allocation leaves its error behind)
     b->p = nullptr;
@@ -291,13 +283,7 @@ grb_info ewm_alloc(DevBuf* b, size_t bytes) {
   return GRB_SUCCESS;
 }
 
-// one orientation of a result: device arrays and the host copy of the pointers
-struct Side {
-  DevBuf ptr, ind, val;
-  std::vector<Index> h_ptr;
-  Index nnz = 0;
-};
-
+namespace {
 // the call's one work allocation, carved for the larger of the two orientations
 struct MergeWork {
   unsigned int* ctr;                                     // [3] bin sizes, then the 64-bit total (8-byte aligned)
@@ -410,6 +396,8 @@ grb_info merge_side(int op, int dtype, Index m, const CsrArrays& Aa, const CsrAr
   });
 }
 
+}  // namespace
+
 // an orientation is usable when it is there and is not the CSR-only format's alias of the CSR
 bool has_csc(const grb_matrix_s* X) { return X->csc.ptr && !X->csc_alias; }
 
@@ -442,7 +430,6 @@ grb_info attach(grb_matrix C, Side* r, Side* c) {
   C->built = true;
   return matrix_apply_format(C);                       // the CSR-only format: the CSC aliases the CSR
 }
-}  // namespace
 
 grb_info ewise_matrix(grb_matrix C, grb_matrix mask, int op, grb_matrix A, grb_matrix B, bool tran_a, bool tran_b, bool scmp,
                       bool add) {
@@ -468,7 +455,7 @@ grb_info ewise_matrix(grb_matrix C, grb_matrix mask, int op, grb_matrix A, grb_m
   const CsrArrays& Bc = tran_b ? B->csr : B->csc;
   const int mask_f32 = mask ? (mask->dtype == GRB_F32 ? 1 : 0) : 0;
   const size_t segs = merge_max_segs(A->nvals, B->nvals);
-  DevBuf work;
+  EwmBuf work;
   GRB_TRY(ewm_alloc(&work, merge_work_bytes(both && n > m ? n : m, segs)));
   const MergeWork w = carve(work.p, both && n > m ? n : m, segs);
   Side r, c;
@@ -509,7 +496,7 @@ grb_info sort_side(const CsrArrays& X, Index m, Index n, Side* out) {
   GRB_TRY(ewm_alloc(&out->ptr, 4 * ((size_t)n + 1)));
   GRB_TRY(ewm_alloc(&out->ind, 4 * (size_t)(nv > 0 ? nv : 1)));
   GRB_TRY(ewm_alloc(&out->val, 4 * (size_t)(nv > 0 ? nv : 1)));
-  DevBuf work;
+  EwmBuf work;
   GRB_TRY(ewm_alloc(&work, 12 * (size_t)nv));
   unsigned long long* keys = (unsigned long long*)work.p;
   unsigned int* pay = (unsigned int*)(keys + nv);

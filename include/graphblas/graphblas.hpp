@@ -1130,6 +1130,41 @@ Info transpose(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, const Matri
   return detail::refresh_result(C);
 }
 
+// extract (operations.hpp:355-410; the reference prints "not implemented yet" for all three): the subvector w = u(indices),
+// the submatrix C = op(A)(row_indices, col_indices) and the column w = op(A)(row_indices, col_index), on the device
+// (grb_hip.h).  A null list is GrB_ALL: every index in order, its count the dimension it stands for.  A mask is
+// GrB_NOT_IMPLEMENTED; accum is ignored.
+namespace detail {
+inline const grb_index* list_of(const std::vector<Index>* v) { return v ? v->data() : static_cast<const grb_index*>(NULL); }
+}  // namespace detail
+
+template <typename W, typename M, typename U, typename BinaryOpT>
+Info extract(Vector<W>* w, const Vector<M>* mask, BinaryOpT accum, const Vector<U>* u, const std::vector<Index>* indices,
+             Index nindices, Descriptor* desc) {
+  if (w == NULL || u == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  return to_info(grb_vector_extract(GRB_H(w), GRB_H(mask), detail::accum_of(accum), GRB_H(u), detail::list_of(indices), nindices,
+                                    desc->handle()));
+}
+
+template <typename c, typename m, typename a, typename BinaryOpT>
+Info extract(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, const Matrix<a>* A, const std::vector<Index>* row_indices,
+             Index nrows, const std::vector<Index>* col_indices, Index ncols, Descriptor* desc) {
+  if (C == NULL || A == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  Info i = to_info(grb_matrix_extract(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), detail::accum_of(accum),
+                                      A->handle(), detail::list_of(row_indices), nrows, detail::list_of(col_indices), ncols,
+                                      desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
+template <typename W, typename M, typename a, typename BinaryOpT>
+Info extract(Vector<W>* w, const Vector<M>* mask, BinaryOpT accum, const Matrix<a>* A, const std::vector<Index>* row_indices,
+             Index nrows, Index col_index, Descriptor* desc) {
+  if (w == NULL || A == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  return to_info(grb_matrix_extract_col(GRB_H(w), GRB_H(mask), detail::accum_of(accum), A->handle(), detail::list_of(row_indices),
+                                        nrows, col_index, desc->handle()));
+}
+
 #undef GRB_H
 }  // namespace graphblas
 

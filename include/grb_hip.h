@@ -308,6 +308,42 @@ grb_info grb_matrix_eWiseMult(grb_matrix C, grb_matrix mask, grb_accum accum, gr
  * its own format): two device copies when A has both, a device sort of A's CSR when A is CSR only.  So transpose with
  * INP0 = TRAN is how a product result gets a CSC.  Aliasing, error codes and C after an error as for eWiseAdd. */
 grb_info grb_transpose(grb_matrix C, grb_matrix mask, grb_accum accum, grb_matrix A, grb_descriptor desc);
+/* extract   operations.hpp:355-410 (subvector, submatrix, matrix column; the reference prints "not implemented yet" and
+ * returns GrB_NOT_IMPLEMENTED for all three).  Index lists are host arrays, as the reference's const std::vector<Index>*;
+ * a null list means every index in order (GrB_ALL) and its count must then be the dimension it stands for.  Lists may be
+ * in any order and may hold duplicates: a duplicate repeats a row, a column or an element.  desc == NULL: the defaults.
+ * accum and the descriptor fields other than GrB_INP0 are ignored: the output is replaced.  A mask: GRB_NOT_IMPLEMENTED
+ * (a caller who wants one applies grb_matrix_eWiseAdd under it afterwards).  The same inputs give the same bits.
+ *
+ * grb_matrix_extract: C = op(A)(I, J).  op(A) is A, or A^T under GrB_INP0 = GrB_TRAN, read from A's CSC as grb_mxm reads
+ * it (a transposed operand without a CSC of its own: GRB_INVALID_OBJECT).  C is nrows x ncols and C(i, j) =
+ * op(A)(I[i], J[j]) wherever that entry is stored -- stored zeros count, values are copied bit for bit -- with columns
+ * ascending in every row.  A and C both GRB_F32 or both GRB_I32, else GRB_NOT_IMPLEMENTED.  C may be A.  C gets its CSR,
+ * and also a CSC (the same extraction with I and J exchanged over op(A)'s other orientation: the same entries and bits)
+ * when that orientation exists; otherwise C is CSR only, as a product result.  A C of the CSR-only format aliases its CSC.
+ *
+ * grb_matrix_extract_col: w = op(A)(I, j): column col_index of A read from its CSC (A without a CSC of its own:
+ * GRB_INVALID_OBJECT), or row col_index of A under GrB_INP0 = GrB_TRAN, read from the CSR.  w has size nrows and becomes
+ * a sparse vector holding entry k wherever op(A)(I[k], j) is stored, indices ascending.  w of A's type, f32 or i32, else
+ * GRB_NOT_IMPLEMENTED.
+ *
+ * grb_vector_extract: w = u(I); w has size nindices.  A dense u gives a dense w with w[k] = u[I[k]]; a sparse u (indices
+ * ascending, as every operation of this library leaves them) a sparse w with entry k wherever I[k] is stored in u, indices
+ * ascending.  Any element type, w of u's (else GRB_DOMAIN_MISMATCH); w may be u.
+ *
+ * On every error the output keeps what it held.  A null handle or an unbuilt input: GRB_UNINITIALIZED_OBJECT; nrows /
+ * ncols / nindices that differ from the output's shape, or a null list whose count is not the dimension of op(A) / u:
+ * GRB_DIMENSION_MISMATCH; an index (col_index included) < 0 or >= the dimension it addresses, found before anything is
+ * written: GRB_INDEX_OUT_OF_BOUNDS; more than INT32_MAX entries in the result (possible through duplicates), or a failed
+ * device allocation: GRB_OUT_OF_MEMORY.  A count of zero is legal: an empty matrix or vector of that shape. */
+grb_info grb_matrix_extract(grb_matrix C, grb_matrix mask, grb_accum accum, grb_matrix A,
+                            const grb_index* row_indices, grb_index nrows,
+                            const grb_index* col_indices, grb_index ncols, grb_descriptor desc);
+grb_info grb_matrix_extract_col(grb_vector w, grb_vector mask, grb_accum accum, grb_matrix A,
+                                const grb_index* row_indices, grb_index nrows, grb_index col_index,
+                                grb_descriptor desc);
+grb_info grb_vector_extract(grb_vector w, grb_vector mask, grb_accum accum, grb_vector u,
+                            const grb_index* indices, grb_index nindices, grb_descriptor desc);
 /* reduce (matrix -> scalar)   operations.hpp:662-680 -> backend :1032-1059 (reduce.hpp:81-91) */
 grb_info grb_reduce_matrix_scalar(double* val, grb_accum accum, grb_monoid op, grb_matrix A, grb_descriptor desc);
 /* traceMxmTranspose (extension)   operations.hpp:698-711 -> backend :1076-1108 (trace.hpp:10-52):
