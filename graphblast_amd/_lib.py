@@ -112,6 +112,10 @@ _SIGS = {
     "grb_matrix_extract": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp],
     "grb_matrix_extract_col": [_vp, _vp, _i, _vp, _vp, _i, _i, _vp],
     "grb_vector_extract": [_vp, _vp, _i, _vp, _vp, _i, _vp],
+    "grb_matrix_assign": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp],
+    "grb_matrix_assign_scalar": [_vp, _vp, _i, _d, _vp, _i, _vp, _i, _vp],
+    "grb_matrix_assign_col": [_vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "grb_matrix_assign_row": [_vp, _vp, _i, _vp, _i, _vp, _i, _vp],
     "grb_matrix_nrows": [_vp, _ip],
     "grb_matrix_ncols": [_vp, _ip],
     "grb_matrix_nvals": [_vp, _ip],

@@ -493,6 +493,37 @@ def extract(out, mask, accum, src, rows, cols, desc):
     return lib.grb_vector_extract(_h(out), _h(mask), _accum(accum), _h(src), ptr(r), nr, _h(desc))
 
 
+def assign_matrix(Cm, mask, accum, src, rows, cols, desc):
+    """graphblas::assign into a matrix (GrB_assign without GrB_REPLACE), the form by the type of src: a Matrix --
+    C(rows, cols) = op(A); a Vector -- C(rows, j) = u when cols is an int, C(i, cols) = u when rows is one; a number --
+    C(rows, cols) = val.  rows / cols are None (GrB_ALL) or anything np.asarray(..., np.int32) takes, in any order,
+    without repeats (a repeated index -> GrB_INVALID_INDEX).  accum is None or a name of BINARY_OPS, applied as
+    accum(c, t).  Without an accum the entries of C inside rows x cols that the source does not store are deleted; with a
+    Matrix mask (matrix and number forms) C changes only where the mask stores a nonzero (GrB_MASK = GrB_SCMP inverts it).
+    Stored zeros count; f32 or i32, src of C's type; C may be src or the mask; C unchanged on every error (grb_hip.h lists
+    the codes).  Returns the info code."""
+    lib = _lib.load()
+    ptr = lambda a: None if a is None else a.ctypes.data
+    op = -1 if accum is None else BINARY_OPS.index(accum)
+    if isinstance(src, Matrix):
+        r, nr = _index_list(rows, Cm.nrows())
+        c, nc = _index_list(cols, Cm.ncols())
+        return lib.grb_matrix_assign(_h(Cm), _h(mask), op, _h(src), ptr(r), nr, ptr(c), nc, _h(desc))
+    if isinstance(src, Vector):
+        row_is_int = isinstance(rows, (int, np.integer))
+        col_is_int = isinstance(cols, (int, np.integer))
+        if row_is_int == col_is_int:
+            raise TypeError("assign_matrix(Matrix, Vector): exactly one of rows / cols is the row's or column's index")
+        if col_is_int:
+            r, nr = _index_list(rows, Cm.nrows())
+            return lib.grb_matrix_assign_col(_h(Cm), _h(mask), op, _h(src), ptr(r), nr, int(cols), _h(desc))
+        c, nc = _index_list(cols, Cm.ncols())
+        return lib.grb_matrix_assign_row(_h(Cm), _h(mask), op, _h(src), int(rows), ptr(c), nc, _h(desc))
+    r, nr = _index_list(rows, Cm.nrows())
+    c, nc = _index_list(cols, Cm.ncols())
+    return lib.grb_matrix_assign_scalar(_h(Cm), _h(mask), op, float(src), ptr(r), nr, ptr(c), nc, _h(desc))
+
+
 def tril(Cm, A, desc):
     return _lib.load().grb_matrix_tril(_h(Cm), _h(A), _h(desc))
 

@@ -885,6 +885,26 @@ grb_info attach(grb_matrix C, Side* r, Side* c);
 grb_info extract_matrix(grb_matrix C, grb_matrix A, const Index* rows, Index nrows, const Index* cols, Index ncols, bool tran);
 grb_info extract_matrix_col(grb_vector w, grb_matrix A, const Index* rows, Index nrows, Index col, bool tran);
 grb_info extract_vector(grb_vector w, grb_vector u, const Index* indices, Index nindices);
+// an index list of one call (extract.hip): validated on the host, on the device when it is not null, inverted on demand
+struct IndexList {
+  const Index* host = nullptr;                           // nullptr: all of 0 .. dim - 1, in order
+  Index n = 0, dim = 0;
+  bool sorted = true;                                    // non-decreasing (a null list is)
+  EwmBuf d_list, d_ptr, d_pos;
+  const Index* dev() const { return (const Index*)d_list.p; }
+  const Index* jptr() const { return (const Index*)d_ptr.p; }
+  const Index* jpos() const { return (const Index*)d_pos.p; }
+};
+grb_info list_check(IndexList* L, const Index* host, Index n, Index dim);
+grb_info list_upload(IndexList* L);
+// jptr[c] .. jptr[c + 1]: the places of c in the list (and jpos, the places themselves, for a list in no order)
+grb_info list_invert(IndexList* L);
+// assign_matrix.hip: the four matrix assign forms (grb_hip.h); accum_op < 0: none
+grb_info assign_matrix(grb_matrix C, grb_matrix mask, int accum_op, grb_matrix A, const Index* rows, Index nrows, const Index* cols,
+                       Index ncols, bool tran, bool scmp);
+grb_info assign_matrix_scalar(grb_matrix C, grb_matrix mask, int accum_op, double val, const Index* rows, Index nrows,
+                              const Index* cols, Index ncols, bool scmp);
+grb_info assign_matrix_vector(grb_matrix C, int accum_op, grb_vector u, const Index* list, Index nlist, Index fixed, bool is_col);
 // objects.hip: the CSR-only format's aliasing of a built matrix (GRB_SPARSE_MATRIX_FORMAT = 1; nothing otherwise)
 grb_info matrix_apply_format(grb_matrix A);
 

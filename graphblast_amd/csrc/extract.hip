@@ -309,17 +309,9 @@ inline int xt_bits(Index dim) {
   return b;
 }
 
-// an index list of one call: validated on the host, on the device when it is not null, inverted on demand
-struct IndexList {
-  const Index* host = nullptr;                           // nullptr: all of 0 .. dim - 1, in order
-  Index n = 0, dim = 0;
-  bool sorted = true;                                    // non-decreasing (a null list is)
-  EwmBuf d_list, d_ptr, d_pos;
-  const Index* dev() const { return (const Index*)d_list.p; }
-  const Index* jptr() const { return (const Index*)d_ptr.p; }
-  const Index* jpos() const { return (const Index*)d_pos.p; }
-};
+}  // namespace
 
+// (IndexList: common.hpp -- assign_matrix.hip validates and inverts its lists the same way)
 grb_info list_check(IndexList* L, const Index* host, Index n, Index dim) {
   L->host = host;
   L->n = n;
@@ -365,6 +357,8 @@ grb_info list_invert(IndexList* L) {
   GRB_HIP_TRY(hipStreamSynchronize(s));                  // (the cursors are freed on the way out)
   return GRB_SUCCESS;
 }
+
+namespace {
 
 template <int kMode>
 grb_info launch_rows(hipStream_t s, const unsigned int* nbin, const Index* l_short, const Index* l_wave, const Index* seg_row,

@@ -1165,6 +1165,69 @@ Info extract(Vector<W>* w, const Vector<M>* mask, BinaryOpT accum, const Matrix<
                                         nrows, col_index, desc->handle()));
 }
 
+// assign, matrix forms (operations.hpp:441-551; the reference prints "assign matrix variant not implemented yet" for all
+// four): C(row_indices, col_indices) = A, C(row_indices, col_index) = u, C(row_index, col_indices) = u and
+// C(row_indices, col_indices) = val, on the device (grb_hip.h).  A null list is GrB_ALL.  The accum is applied as
+// accum(c, t): its operator crosses the ABI as the functor's grb_op (every functor of GRB_BINARYOP carries one); a functor
+// type without it is GrB_NOT_IMPLEMENTED.  The vector mask of the row and column forms is GrB_NOT_IMPLEMENTED.
+namespace detail {
+template <typename A, typename = void> struct accum_code { static const int value = -2; };
+template <typename A> struct accum_code<A, typename std::enable_if<(A::grb_op >= 0)>::type> { static const int value = A::grb_op; };
+// -1: no accum; -2: a functor this backend has no operator code for
+template <typename A> inline int accum_op_of(const A&) { return accum_present<A>::value ? accum_code<A>::value : -1; }
+}  // namespace detail
+
+template <typename c, typename m, typename a, typename BinaryOpT>
+Info assign(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, const Matrix<a>* A, const std::vector<Index>* row_indices,
+            Index nrows, const std::vector<Index>* col_indices, Index ncols, Descriptor* desc) {
+  if (C == NULL || A == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  const int op = detail::accum_op_of(accum);
+  if (op < -1) return GrB_NOT_IMPLEMENTED;
+  Info i = to_info(grb_matrix_assign(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), op, A->handle(),
+                                     detail::list_of(row_indices), nrows, detail::list_of(col_indices), ncols, desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
+template <typename c, typename M, typename U, typename BinaryOpT>
+Info assign(Matrix<c>* C, const Vector<M>* mask, BinaryOpT accum, const Vector<U>* u, const std::vector<Index>* row_indices,
+            Index nrows, Index col_index, Descriptor* desc) {
+  if (C == NULL || u == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  const int op = detail::accum_op_of(accum);
+  if (op < -1) return GrB_NOT_IMPLEMENTED;
+  Info i = to_info(grb_matrix_assign_col(C->handle(), GRB_H(mask), op, GRB_H(u), detail::list_of(row_indices), nrows, col_index,
+                                         desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
+template <typename c, typename M, typename U, typename BinaryOpT>
+Info assign(Matrix<c>* C, const Vector<M>* mask, BinaryOpT accum, const Vector<U>* u, Index row_index,
+            const std::vector<Index>* col_indices, Index ncols, Descriptor* desc) {
+  if (C == NULL || u == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  const int op = detail::accum_op_of(accum);
+  if (op < -1) return GrB_NOT_IMPLEMENTED;
+  Info i = to_info(grb_matrix_assign_row(C->handle(), GRB_H(mask), op, GRB_H(u), row_index, detail::list_of(col_indices), ncols,
+                                         desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
+// (a pointer is no constant: a non-const Matrix<a>* operand selects the matrix form above, as a const one does)
+template <typename c, typename m, typename T, typename BinaryOpT>
+typename std::enable_if<!std::is_pointer<T>::value, Info>::type
+assign(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, T val, const std::vector<Index>* row_indices, Index nrows,
+       const std::vector<Index>* col_indices, Index ncols, Descriptor* desc) {
+  if (C == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  const int op = detail::accum_op_of(accum);
+  if (op < -1) return GrB_NOT_IMPLEMENTED;
+  Info i = to_info(grb_matrix_assign_scalar(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), op,
+                                            static_cast<double>(val), detail::list_of(row_indices), nrows,
+                                            detail::list_of(col_indices), ncols, desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
 #undef GRB_H
 }  // namespace graphblas
 

@@ -344,6 +344,47 @@ grb_info grb_matrix_extract_col(grb_vector w, grb_vector mask, grb_accum accum, 
                                 grb_descriptor desc);
 grb_info grb_vector_extract(grb_vector w, grb_vector mask, grb_accum accum, grb_vector u,
                             const grb_index* indices, grb_index nindices, grb_descriptor desc);
+/* assign, matrix forms   operations.hpp:441-551 (C(I, J) = A, C(I, j) = u, C(i, J) = u, C(I, J) = val; the reference prints
+ * "assign matrix variant not implemented yet" and returns GrB_NOT_IMPLEMENTED for all four).  GraphBLAS's GrB_assign
+ * without GrB_REPLACE.  Index lists are host arrays in any order; a null list is GrB_ALL and its count must then be C's
+ * dimension.  A repeated index makes the result undefined in GraphBLAS: here it is GRB_INVALID_INDEX, found before anything
+ * is written.  accum_op is -1 for no accum, else a grb_binary_op (all 17), applied as accum(c, t) in C's element type by the
+ * operator dispatch of grb_matrix_apply's BIND forms.  desc == NULL: the defaults; fields other than GrB_INP0 (the matrix
+ * form) and GrB_MASK are ignored.
+ *
+ * Let T hold the source at its targets -- T(I[i], J[j]) = op(A)(i, j) wherever that is stored; T(I[k], j) = u[k];
+ * T(i, J[k]) = u[k]; val at every position of I x J -- and R = I x J.  Position by position, Z is: in T and in C:
+ * accum(c, t), or t without an accum; in T only: t; in C only inside R: kept under an accum, DELETED without one; in C only
+ * outside R: kept bit for bit.  With a mask M of C's shape (the matrix and the constant form) the new C is Z where M stores a
+ * nonzero value and the old C elsewhere, inverted under GrB_MASK = GrB_SCMP (mxm's rule).  Stored zeros count everywhere:
+ * nothing is dropped by value.  Columns ascend in every row; the same inputs give the same bits.  op(A) is A, or A^T under
+ * GrB_INP0 = GrB_TRAN, read from A's CSC as grb_matrix_extract reads it.  u may be sparse (its stored entries) or dense
+ * (every element counts as stored).  val becomes C's element type.  C, A / u all GRB_F32 or all GRB_I32, else
+ * GRB_NOT_IMPLEMENTED; the mask may be either type.  The vector mask of the row and column forms: GRB_NOT_IMPLEMENTED.
+ * C may be A or the mask.  A C that was never built counts as empty.
+ *
+ * C gets its CSR, and also a CSC (the same routine over the other orientations with I and J exchanged: the same entries
+ * and bits) when the old C, op(A) and the mask each have their other orientation; otherwise C is CSR only, as a product
+ * result.  A C of the CSR-only format aliases its CSC.
+ *
+ * On every error C keeps what it held.  A null handle or an unbuilt input: GRB_UNINITIALIZED_OBJECT; nrows / ncols that
+ * differ from op(A)'s shape or u's size, a mask not of C's shape, or a null list whose count is not C's dimension:
+ * GRB_DIMENSION_MISMATCH; an index, row_index or col_index outside C: GRB_INDEX_OUT_OF_BOUNDS; a repeated index:
+ * GRB_INVALID_INDEX; a transposed A without a CSC of its own: GRB_INVALID_OBJECT; more than INT32_MAX entries in the result
+ * (a 64-bit total, checked before C is touched), or a failed device allocation: GRB_OUT_OF_MEMORY.  A count of zero is
+ * legal and leaves C as it was. */
+grb_info grb_matrix_assign(grb_matrix C, grb_matrix mask, int accum_op, grb_matrix A,
+                           const grb_index* row_indices, grb_index nrows,
+                           const grb_index* col_indices, grb_index ncols, grb_descriptor desc);
+grb_info grb_matrix_assign_scalar(grb_matrix C, grb_matrix mask, int accum_op, double val,
+                                  const grb_index* row_indices, grb_index nrows,
+                                  const grb_index* col_indices, grb_index ncols, grb_descriptor desc);
+grb_info grb_matrix_assign_col(grb_matrix C, grb_vector mask, int accum_op, grb_vector u,
+                               const grb_index* row_indices, grb_index nrows, grb_index col_index,
+                               grb_descriptor desc);
+grb_info grb_matrix_assign_row(grb_matrix C, grb_vector mask, int accum_op, grb_vector u,
+                               grb_index row_index, const grb_index* col_indices, grb_index ncols,
+                               grb_descriptor desc);
 /* reduce (matrix -> scalar)   operations.hpp:662-680 -> backend :1032-1059 (reduce.hpp:81-91) */
 grb_info grb_reduce_matrix_scalar(double* val, grb_accum accum, grb_monoid op, grb_matrix A, grb_descriptor desc);
 /* traceMxmTranspose (extension)   operations.hpp:698-711 -> backend :1076-1108 (trace.hpp:10-52):
