@@ -112,6 +112,8 @@ _SIGS = {
     "grb_matrix_extract": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp],
     "grb_matrix_extract_col": [_vp, _vp, _i, _vp, _vp, _i, _i, _vp],
     "grb_vector_extract": [_vp, _vp, _i, _vp, _vp, _i, _vp],
+    "grb_matrix_select": [_vp, _vp, _i, _i, _d, _vp, _vp],
+    "grb_vector_select": [_vp, _vp, _i, _i, _d, _vp, _vp],
     "grb_matrix_assign": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp],
     "grb_matrix_assign_scalar": [_vp, _vp, _i, _d, _vp, _i, _vp, _i, _vp],
     "grb_matrix_assign_col": [_vp, _vp, _i, _vp, _vp, _i, _i, _vp],

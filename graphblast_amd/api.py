@@ -493,6 +493,25 @@ def extract(out, mask, accum, src, rows, cols, desc):
     return lib.grb_vector_extract(_h(out), _h(mask), _accum(accum), _h(src), ptr(r), nr, _h(desc))
 
 
+SELECT_OPS = ["tril", "triu", "diag", "offdiag", "rowle", "rowgt", "colle", "colgt",
+              "valueeq", "valuene", "valuelt", "valuele", "valuegt", "valuege"]             # grb_select_op
+
+
+def select(out, mask, accum, op, src, thunk, desc):
+    """GraphBLAS's select: out keeps exactly the stored entries of op(src) for which the predicate holds, values bit for
+    bit, order unchanged.  op is a name of SELECT_OPS; with i, j the entry's row and column in op(src) (a Vector: j = 0),
+    a its value and k the thunk: tril j <= i + k, triu j >= i + k, diag j == i + k, offdiag j != i + k, rowle i <= k,
+    rowgt i > k, colle j <= k, colgt j > k, valueeq / valuene / valuelt / valuele / valuegt / valuege compare a with k.
+    select(C, None, None, "valuene", A, 0, desc) drops the stored zeros; "tril" with thunk 0 is the lower triangle.
+    Matrix: f32 or i32, C of A's type and of op(A)'s shape; C may be A; GrB_INP0 = GrB_TRAN reads A^T from A's CSC; C gets a
+    CSC too when op(A) has its other orientation.  Vector: w of u's size and type becomes sparse; w may be u.  A positional
+    thunk must be an integer, a value thunk on i32 an integer that fits (else GrB_INVALID_VALUE); a mask ->
+    GrB_NOT_IMPLEMENTED; the output unchanged on every error (grb_hip.h lists the codes).  Returns the info code."""
+    k = SELECT_OPS.index(op)
+    fn = "grb_matrix_select" if isinstance(out, Matrix) else "grb_vector_select"
+    return getattr(_lib.load(), fn)(_h(out), _h(mask), _accum(accum), k, float(thunk), _h(src), _h(desc))
+
+
 def assign_matrix(Cm, mask, accum, src, rows, cols, desc):
     """graphblas::assign into a matrix (GrB_assign without GrB_REPLACE), the form by the type of src: a Matrix --
     C(rows, cols) = op(A); a Vector -- C(rows, j) = u when cols is an int, C(i, cols) = u when rows is one; a number --

@@ -905,6 +905,9 @@ grb_info assign_matrix(grb_matrix C, grb_matrix mask, int accum_op, grb_matrix A
 grb_info assign_matrix_scalar(grb_matrix C, grb_matrix mask, int accum_op, double val, const Index* rows, Index nrows,
                               const Index* cols, Index ncols, bool scmp);
 grb_info assign_matrix_vector(grb_matrix C, int accum_op, grb_vector u, const Index* list, Index nlist, Index fixed, bool is_col);
+// select.hip: C = select(op(A), op, thunk), w = select(u, op, thunk) (grb_hip.h: the entries that pass a grb_select_op)
+grb_info select_matrix(grb_matrix C, grb_matrix A, int op, double thunk, bool tran);
+grb_info select_vector(grb_vector w, grb_vector u, int op, double thunk);
 // objects.hip: the CSR-only format's aliasing of a built matrix (GRB_SPARSE_MATRIX_FORMAT = 1; nothing otherwise)
 grb_info matrix_apply_format(grb_matrix A);
 

@@ -1165,6 +1165,45 @@ Info extract(Vector<W>* w, const Vector<M>* mask, BinaryOpT accum, const Matrix<
                                         nrows, col_index, desc->handle()));
 }
 
+// select (GraphBLAS's GrB_select with the predefined index-unary operators; the reference has no such operation): the
+// stored entries of op(A), or of u, for which the predicate holds with the thunk, on the device (grb_hip.h).  i, j: the
+// entry's row and column in op(A) (a vector: j = 0), a: its value, k: the thunk.  GrB_SEL_VALUENE with thunk 0 drops the
+// stored zeros.  A mask is GrB_NOT_IMPLEMENTED; accum is ignored.  The enumerators equal grb_select_op's.
+enum SelectOp {
+  GrB_SEL_TRIL = GRB_SEL_TRIL,         // j <= i + k
+  GrB_SEL_TRIU = GRB_SEL_TRIU,         // j >= i + k
+  GrB_SEL_DIAG = GRB_SEL_DIAG,         // j == i + k
+  GrB_SEL_OFFDIAG = GRB_SEL_OFFDIAG,   // j != i + k
+  GrB_SEL_ROWLE = GRB_SEL_ROWLE,       // i <= k
+  GrB_SEL_ROWGT = GRB_SEL_ROWGT,       // i > k
+  GrB_SEL_COLLE = GRB_SEL_COLLE,       // j <= k
+  GrB_SEL_COLGT = GRB_SEL_COLGT,       // j > k
+  GrB_SEL_VALUEEQ = GRB_SEL_VALUEEQ,   // a == k
+  GrB_SEL_VALUENE = GRB_SEL_VALUENE,   // a != k
+  GrB_SEL_VALUELT = GRB_SEL_VALUELT,   // a < k
+  GrB_SEL_VALUELE = GRB_SEL_VALUELE,   // a <= k
+  GrB_SEL_VALUEGT = GRB_SEL_VALUEGT,   // a > k
+  GrB_SEL_VALUEGE = GRB_SEL_VALUEGE    // a >= k
+};
+
+template <typename c, typename m, typename a, typename BinaryOpT>
+Info select(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SelectOp op, const Matrix<a>* A, double thunk,
+            Descriptor* desc) {
+  if (C == NULL || A == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  Info i = to_info(grb_matrix_select(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), detail::accum_of(accum),
+                                     static_cast<int>(op), thunk, A->handle(), desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
+template <typename W, typename M, typename U, typename BinaryOpT>
+Info select(Vector<W>* w, const Vector<M>* mask, BinaryOpT accum, SelectOp op, const Vector<U>* u, double thunk,
+            Descriptor* desc) {
+  if (w == NULL || u == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  return to_info(grb_vector_select(GRB_H(w), GRB_H(mask), detail::accum_of(accum), static_cast<int>(op), thunk, GRB_H(u),
+                                   desc->handle()));
+}
+
 // assign, matrix forms (operations.hpp:441-551; the reference prints "assign matrix variant not implemented yet" for all
 // four): C(row_indices, col_indices) = A, C(row_indices, col_index) = u, C(row_index, col_indices) = u and
 // C(row_indices, col_indices) = val, on the device (grb_hip.h).  A null list is GrB_ALL.  The accum is applied as

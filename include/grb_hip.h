@@ -85,6 +85,17 @@ typedef enum {
   GRB_UNARY_BIND_FIRST, GRB_UNARY_BIND_SECOND, GRB_N_UNARY_OPS
 } grb_unary_op;
 
+/* Predicates of select (GraphBLAS C API 2.0, GrB_select with the predefined index-unary operators).  i, j: the row and
+ * column of the entry in op(A) (a vector is an n x 1 matrix: j = 0), a: its value, k: the thunk.
+ *   TRIL j <= i + k   TRIU j >= i + k   DIAG j == i + k   OFFDIAG j != i + k
+ *   ROWLE i <= k   ROWGT i > k   COLLE j <= k   COLGT j > k
+ *   VALUEEQ a == k   VALUENE a != k   VALUELT a < k   VALUELE a <= k   VALUEGT a > k   VALUEGE a >= k
+ * GRB_SEL_VALUENE with thunk 0 is "drop stored zeros". */
+typedef enum {
+  GRB_SEL_TRIL = 0, GRB_SEL_TRIU, GRB_SEL_DIAG, GRB_SEL_OFFDIAG, GRB_SEL_ROWLE, GRB_SEL_ROWGT, GRB_SEL_COLLE, GRB_SEL_COLGT,
+  GRB_SEL_VALUEEQ, GRB_SEL_VALUENE, GRB_SEL_VALUELT, GRB_SEL_VALUELE, GRB_SEL_VALUEGT, GRB_SEL_VALUEGE, GRB_N_SELECT_OPS
+} grb_select_op;
+
 /* `accum` argument: the reference only tests its presence
  * (typeid(accum).name().size() > 1, backend/cuda/spmv.hpp:34-40). */
 typedef enum { GRB_ACCUM_NULL = 0, GRB_ACCUM_PRESENT = 1 } grb_accum;
@@ -385,6 +396,38 @@ grb_info grb_matrix_assign_col(grb_matrix C, grb_vector mask, int accum_op, grb_
 grb_info grb_matrix_assign_row(grb_matrix C, grb_vector mask, int accum_op, grb_vector u,
                                grb_index row_index, const grb_index* col_indices, grb_index ncols,
                                grb_descriptor desc);
+/* select   (GraphBLAS C API 2.0, GrB_select; the reference has no such operation, so the definition is GraphBLAS's own.)
+ * The result keeps exactly the stored entries for which the predicate select_op (a grb_select_op, above) holds with the
+ * thunk; values are copied bit for bit and the order is unchanged.  Stored zeros are entries like any other, so
+ * GRB_SEL_VALUENE with thunk 0 is how they are dropped.  desc == NULL: the defaults.  accum and the descriptor fields
+ * other than GrB_INP0 are ignored: the output is replaced.  A mask: GRB_NOT_IMPLEMENTED, as for extract and transpose (a
+ * caller who wants one applies grb_matrix_eWiseAdd under it afterwards).  The same inputs give the same bits.
+ *
+ * The thunk crosses the ABI as a double.  Positional operators (TRIL .. COLGT): it must be integer-valued, else
+ * GRB_INVALID_VALUE, and is used in 64-bit arithmetic, so i + k cannot wrap for any thunk (+-2^40 included).  Value
+ * operators on f32: the thunk is rounded to float and the comparison is IEEE f32 (NaN passes only VALUENE; -0.0f == 0.0f).
+ * Value operators on i32: the thunk must be an integer in [INT32_MIN, INT32_MAX], else GRB_INVALID_VALUE (rounding it
+ * silently would turn >= 2.5 into >= 2).
+ *
+ * grb_matrix_select: C = select(op(A)).  op(A) is A, or A^T under GrB_INP0 = GrB_TRAN, read from A's CSC as
+ * grb_matrix_extract reads it (a transposed A without a CSC of its own: GRB_INVALID_OBJECT).  C has op(A)'s shape.  A and
+ * C both GRB_F32 or both GRB_I32, else GRB_NOT_IMPLEMENTED.  C holds the kept entries with columns ascending in every row;
+ * rows that lose everything stay as empty rows.  C may be A.  C always gets its CSR, and also a CSC (the same routine over
+ * op(A)'s other orientation with the roles of i and j exchanged in the predicate: the same entries and bits) when that
+ * orientation exists; otherwise C is CSR only, as a product result.  A C of the CSR-only format aliases its CSC.
+ *
+ * grb_vector_select: w = select(u), i the index and j = 0.  w has u's size and u's type (else GRB_DOMAIN_MISMATCH) and
+ * always becomes a sparse vector with ascending indices: from a sparse u the stored entries that pass, from a dense u
+ * every element counts as stored.  w may be u.
+ *
+ * On every error the output keeps what it held; all of them are found before anything of the output is written.  A null
+ * handle or an unbuilt input: GRB_UNINITIALIZED_OBJECT; a C not of op(A)'s shape, or a w not of u's size:
+ * GRB_DIMENSION_MISMATCH; select_op outside the enum, or a thunk the rules above reject: GRB_INVALID_VALUE; a failed device
+ * allocation: GRB_OUT_OF_MEMORY.  The result is never larger than the input, so there is no INT32_MAX case. */
+grb_info grb_matrix_select(grb_matrix C, grb_matrix mask, grb_accum accum, int select_op, double thunk,
+                           grb_matrix A, grb_descriptor desc);
+grb_info grb_vector_select(grb_vector w, grb_vector mask, grb_accum accum, int select_op, double thunk,
+                           grb_vector u, grb_descriptor desc);
 /* reduce (matrix -> scalar)   operations.hpp:662-680 -> backend :1032-1059 (reduce.hpp:81-91) */
 grb_info grb_reduce_matrix_scalar(double* val, grb_accum accum, grb_monoid op, grb_matrix A, grb_descriptor desc);
 /* traceMxmTranspose (extension)   operations.hpp:698-711 -> backend :1076-1108 (trace.hpp:10-52):
