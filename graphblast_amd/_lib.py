@@ -108,6 +108,7 @@ _SIGS = {
     "grb_matrix_eWiseMult_vector": [_vp, _i, _vp, _vp, _vp],
     "grb_matrix_eWiseAdd": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "grb_matrix_eWiseMult": [_vp, _vp, _i, _i, _vp, _vp, _vp],
+    "grb_kronecker": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "grb_transpose": [_vp, _vp, _i, _vp, _vp],
     "grb_matrix_extract": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp],
     "grb_matrix_extract_col": [_vp, _vp, _i, _vp, _vp, _i, _i, _vp],

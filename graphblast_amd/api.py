@@ -448,6 +448,18 @@ def mxm(Cm, mask, accum, op, A, B, desc):
     return _lib.load().grb_mxm(_h(Cm), _h(mask), _accum(accum), _semiring_id(op), _h(A), _h(B), _h(desc))
 
 
+def kronecker(Cm, mask, accum, op, A, B, desc):
+    """GraphBLAS's kronecker: C = op(A) (x) op(B) (GrB_INP0 / GrB_INP1 = GrB_TRAN transpose an operand, read from its
+    CSC).  With op(A) mA x nA and op(B) mB x nB, C is (mA * mB) x (nA * nB) and C(iA * mB + iB, jA * nB + jB) = mul(a, b)
+    wherever both entries are stored, mul the multiply of op (a semiring name or a registered id; its monoid is not used), a
+    first; stored zeros count, so C.nvals() == A.nvals() * B.nvals().  f32 or i32, all three alike (GrB_NOT_IMPLEMENTED
+    otherwise); a mask -> GrB_NOT_IMPLEMENTED; C may be A, B or both; shapes -> GrB_DIMENSION_MISMATCH, a transposed operand
+    without its CSC -> GrB_INVALID_OBJECT, more than INT32_MAX entries -> GrB_OUT_OF_MEMORY, an unknown semiring id ->
+    GrB_INVALID_VALUE (C unchanged on every error).  C gets a CSC too when both operands have their other orientation.
+    Returns the info code."""
+    return _lib.load().grb_kronecker(_h(Cm), _h(mask), _accum(accum), _semiring_id(op), _h(A), _h(B), _h(desc))
+
+
 def transpose(Cm, mask, accum, A, desc):
     """graphblas::transpose: C = A^T, or C = A under GrB_INP0 = GrB_TRAN, with both orientations (a CSR-only A, such as a
     product result, is sorted on the device).  f32 or i32, C of A's type; a mask -> GrB_NOT_IMPLEMENTED; C may be A; C

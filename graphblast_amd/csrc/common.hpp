@@ -908,6 +908,8 @@ grb_info assign_matrix_vector(grb_matrix C, int accum_op, grb_vector u, const In
 // select.hip: C = select(op(A), op, thunk), w = select(u, op, thunk) (grb_hip.h: the entries that pass a grb_select_op)
 grb_info select_matrix(grb_matrix C, grb_matrix A, int op, double thunk, bool tran);
 grb_info select_vector(grb_vector w, grb_vector u, int op, double thunk);
+// kronecker.hip: C = op(A) (x) op(B), the Kronecker product under op's multiply (grb_hip.h)
+grb_info kronecker_matrix(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool tran_a, bool tran_b);
 // objects.hip: the CSR-only format's aliasing of a built matrix (GRB_SPARSE_MATRIX_FORMAT = 1; nothing otherwise)
 grb_info matrix_apply_format(grb_matrix A);
 

@@ -1119,6 +1119,19 @@ Info eWiseMult(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT o
   return detail::refresh_result(C);
 }
 
+// kronecker (GraphBLAS's GrB_kronecker; the reference declares no such operation): C = op(A) (x) op(B),
+// C(iA * mB + iB, jA * nB + jB) = mul(a, b) with op's multiply, on the device (grb_hip.h).  A mask is GrB_NOT_IMPLEMENTED;
+// accum and op's additive monoid are not used
+template <typename c, typename m, typename a, typename b, typename BinaryOpT, typename SemiringT>
+Info kronecker(Matrix<c>* C, const Matrix<m>* mask, BinaryOpT accum, SemiringT op, const Matrix<a>* A, const Matrix<b>* B,
+               Descriptor* desc) {
+  if (C == NULL || A == NULL || B == NULL || desc == NULL) return GrB_UNINITIALIZED_OBJECT;
+  Info i = to_info(grb_kronecker(C->handle(), mask ? mask->handle() : static_cast<grb_matrix>(NULL), detail::accum_of(accum),
+                                 detail::sr_id<SemiringT>(), A->handle(), B->handle(), desc->handle()));
+  if (i != GrB_SUCCESS) return i;
+  return detail::refresh_result(C);
+}
+
 // transpose (operations.hpp:682): C = A^T, or C = A with GrB_INP0 = GrB_TRAN, with both orientations; a mask is
 // GrB_NOT_IMPLEMENTED
 template <typename c, typename m, typename a, typename BinaryOpT>

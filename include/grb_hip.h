@@ -428,6 +428,27 @@ grb_info grb_matrix_select(grb_matrix C, grb_matrix mask, grb_accum accum, int s
                            grb_matrix A, grb_descriptor desc);
 grb_info grb_vector_select(grb_vector w, grb_vector mask, grb_accum accum, int select_op, double thunk,
                            grb_vector u, grb_descriptor desc);
+/* kronecker   (GraphBLAS C API, GrB_kronecker; the reference declares no such operation, so the definition is GraphBLAS's
+ * own.)  C = op(A) (x) op(B): with op(A) mA x nA and op(B) mB x nB, C is (mA * mB) x (nA * nB) and
+ * C(iA * mB + iB, jA * nB + jB) = mul(op(A)(iA, jA), op(B)(iB, jB)) wherever both entries are stored -- stored zeros
+ * count, nothing is dropped by value, so nvals(C) = nvals(A) * nvals(B) -- with columns ascending in every row.  mul is the
+ * multiplicative operator of op, A's value first: all 17 built-in semirings and the ids of grb_semiring_register; the
+ * additive monoid is not used.  op(A) is A, or A^T under GrB_INP0 = GrB_TRAN; op(B) is B, or B^T under GrB_INP1 = GrB_TRAN,
+ * read from that matrix's CSC as grb_mxm reads it.  desc == NULL: the defaults.  A, B and C all GRB_F32 or all GRB_I32,
+ * else GRB_NOT_IMPLEMENTED.  A mask: GRB_NOT_IMPLEMENTED, as for extract, select and transpose (a caller who wants one
+ * applies grb_matrix_eWiseMult under it afterwards).  accum and the other descriptor fields are ignored: C is replaced.
+ * C may be A, B or both.  The same inputs give the same bits.  An operand with no entries gives an empty C of the right
+ * shape.  C always gets its CSR, and also a CSC (the same routine over the other orientations of op(A) and op(B), since
+ * (A (x) B)^T = A^T (x) B^T: the same entries and bits) when op(A) and op(B) both have their other orientation; otherwise
+ * C is CSR only, as a product result.  A C of the CSR-only format aliases its CSC.
+ *
+ * On every error C keeps what it held; all of them are found before anything of C is written.  A null handle or an
+ * unbuilt A or B: GRB_UNINITIALIZED_OBJECT; a C whose shape is not (mA * mB) x (nA * nB), the products taken in 64 bits:
+ * GRB_DIMENSION_MISMATCH; a transposed operand without a CSC of its own (a product result, the CSR-only format):
+ * GRB_INVALID_OBJECT; a semiring id that does not exist: GRB_INVALID_VALUE; nvals(A) * nvals(B) > INT32_MAX as a 64-bit
+ * product, or a failed device allocation: GRB_OUT_OF_MEMORY. */
+grb_info grb_kronecker(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op, grb_matrix A, grb_matrix B,
+                       grb_descriptor desc);
 /* reduce (matrix -> scalar)   operations.hpp:662-680 -> backend :1032-1059 (reduce.hpp:81-91) */
 grb_info grb_reduce_matrix_scalar(double* val, grb_accum accum, grb_monoid op, grb_matrix A, grb_descriptor desc);
 /* traceMxmTranspose (extension)   operations.hpp:698-711 -> backend :1076-1108 (trace.hpp:10-52):
