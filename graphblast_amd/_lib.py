@@ -33,6 +33,11 @@ class AlgoResult(C.Structure):
     _fields_ = [("iterations", C.c_int), ("tight_ms", C.c_float), ("last_value", C.c_double)]
 
 
+class TrussResult(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("supports", C.c_int32), ("edges", C.c_int64), ("result_edges", C.c_int64),
+                ("kmax", C.c_int32), ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -190,6 +195,8 @@ _SIGS = {
     "grb_matrix_tril": [_vp, _vp, _vp],
     "grb_tc": [C.POINTER(C.c_int64), _vp, _vp, _vp, C.POINTER(AlgoResult)],
     "grb_tc_dense_core": [_vp, _i, _i, _i, C.POINTER(TcCoreResult)],
+    "grb_ktruss": [_vp, _vp, _i, _vp, C.POINTER(TrussResult)],
+    "grb_trussness": [_vp, _vp, _vp, C.POINTER(TrussResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

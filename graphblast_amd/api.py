@@ -685,6 +685,36 @@ def tc(A, B, desc):
     return info, n.value, dict(tight_ms=res.tight_ms)
 
 
+def _truss_dict(res):
+    return dict(rounds=res.rounds, supports=res.supports, edges=res.edges, result_edges=res.result_edges, kmax=res.kmax,
+                loop_ms=res.loop_ms)
+
+
+def ktruss(Cm, A, k, desc):
+    """grb_ktruss: Cm = the k-truss of A's graph, the largest subgraph in which every edge lies in at least k - 2 triangles
+    of the subgraph.  A is n x n with a symmetric structure; its values are never read (stored zeros are edges), its
+    diagonal takes no part.  Cm is n x n, f32 or i32 whatever A's type, holds both directions of every surviving edge
+    (columns ascending, rows that lose everything stay empty, CSC = a copy of the CSR) and Cm(i, j) is the edge's support:
+    the common neighbours of i and j inside the truss.  k = 2 is the whole graph with its supports.  Cm may be A; the same
+    inputs give the same bits.  k < 2 -> GrB_INVALID_VALUE; A not square or Cm not n x n -> GrB_DIMENSION_MISMATCH; a type
+    outside f32 / i32 -> GrB_NOT_IMPLEMENTED; an A without its own CSC (a product result) -> GrB_INVALID_OBJECT; an A that
+    is not symmetric -> GrB_INVALID_VALUE (Cm unchanged on every error).  Returns (info, dict(rounds, supports, edges,
+    result_edges, kmax = k, loop_ms))."""
+    res = _lib.TrussResult()
+    info = _lib.load().grb_ktruss(_h(Cm), _h(A), int(k), _h(desc), C.byref(res))
+    return info, _truss_dict(res)
+
+
+def trussness(Cm, A, desc):
+    """grb_trussness: Cm gets the structure of A's graph (A as for ktruss: symmetric structure, values never read, no
+    diagonal) and Cm(i, j) = the largest k such that the edge {i, j} is in the k-truss: 2 for an edge in no triangle.  Types,
+    orientations, aliasing and error codes as for ktruss.  Returns (info, dict(rounds, supports, edges, result_edges,
+    kmax = the largest k with a non-empty truss, loop_ms))."""
+    res = _lib.TrussResult()
+    info = _lib.load().grb_trussness(_h(Cm), _h(A), _h(desc), C.byref(res))
+    return info, _truss_dict(res)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

@@ -319,6 +319,12 @@ grb_info grb::device_exclusive_scan_u32_in(unsigned int* d, long long n, unsigne
   return GRB_SUCCESS;
 }
 
+// ... and left in flight on the context stream: for a loop that reads its results once per round (ktruss.hip)
+grb_info grb::device_exclusive_scan_u32_async(unsigned int* d, long long n, unsigned int* totals) {
+  if (n <= 0) return GRB_SUCCESS;
+  return exclusive_scan_u32(d, n, totals, ctx().stream);
+}
+
 // In-place exclusive scan of n unsigned ints on the context stream (scratch for the tile totals allocated here).
 grb_info grb::device_exclusive_scan_u32(unsigned int* d, long long n) {
   if (n <= 0) return GRB_SUCCESS;

@@ -776,6 +776,7 @@ void free_spmv_plan(SpmvPlan* plan);
 grb_info device_exclusive_scan_u32(unsigned int* d, long long n);   // build.hip
 size_t device_scan_u32_scratch(long long n);                        // bytes of tile totals the scan below needs
 grb_info device_exclusive_scan_u32_in(unsigned int* d, long long n, unsigned int* totals);   // ... in a buffer of the caller's
+grb_info device_exclusive_scan_u32_async(unsigned int* d, long long n, unsigned int* totals);   // ... without the synchronisation
 grb_info device_sort_pairs(unsigned long long* d_keys, unsigned int* d_pay, long long n, int lo_bits, int hi_bits);   // build.hip
 grb_info device_sort_pairs_range(unsigned long long* d_keys, unsigned int* d_pay, long long n, int first_bit, int nbits);
 grb_info device_rank_columns(const Index* d_ind, Index nvals, const Index* d_other_ptr, Index m, Index hot,

@@ -804,6 +804,52 @@ typedef struct {
 } grb_tc_core_result;
 grb_info grb_tc_dense_core(grb_matrix L, int k_want, int method, int dense_from, grb_tc_core_result* res);
 
+/* k-truss and edge trussness (csrc/ktruss.hip).  The reference has no such driver (graphblas/algorithm/), so the
+ * definitions are this header's own; they follow LAGraph's convention, the usual one.
+ *
+ * A is an n x n matrix with the same structure as its transpose.  Stored values are never read: only the structure counts,
+ * so stored zeros are edges like any other.  Diagonal entries take no part and never appear in a result.  G is the simple
+ * undirected graph of A's off-diagonal entries.  For k >= 2 the k-truss of G is the largest subgraph T in which every edge
+ * lies in at least k - 2 triangles of T; it is unique.
+ *
+ * grb_ktruss(C, A, k, desc, result): C is n x n and holds both (i, j) and (j, i) for every edge of T, columns ascending in
+ * every row; C(i, j) is the support of {i, j} in T, the number of common neighbours of i and j within T.  Rows that lose
+ * everything stay as empty rows.  k = 2 returns all of G with its supports -- the only case in which stored supports may be
+ * 0.
+ *
+ * grb_trussness(C, A, desc, result): C has G's structure, both directions, and C(i, j) is the largest k such that {i, j}
+ * is in the k-truss: 2 for an edge in no triangle.
+ *
+ * Both: C's element type is GRB_I32 or GRB_F32, A's is either of the two, independently of C's.  C gets both orientations,
+ * the CSC a copy of the CSR (the result is symmetric); a C of the CSR-only format aliases its CSC, as in the other
+ * operations.  C may be A.  The same inputs give the same bits.  desc == NULL means the defaults; no descriptor field is
+ * read.  result may be NULL.
+ *
+ * How: the working graph stays on the device for the whole call.  A round computes the support of every edge of what is
+ * left -- every edge intersected once, by its endpoint with the longer list -- and drops the edges below k - 2; the call
+ * ends when a round drops nothing.  grb_trussness runs the same rounds for k = 3, 4, ...: what a round drops at level k has
+ * trussness k - 1, a round that drops nothing raises k, and the call ends when nothing is left.  The host reads one record
+ * per round.
+ *
+ * Every error is found before anything of C is written, and C keeps what it held.  A null C or A, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, or C not n x n: GRB_DIMENSION_MISMATCH; k < 2: GRB_INVALID_VALUE; an element type
+ * of A or C outside f32 / i32: GRB_NOT_IMPLEMENTED; an A without a CSC of its own (a product result): GRB_INVALID_OBJECT
+ * -- the caller gets one with grb_transpose under GrB_INP0 = GrB_TRAN; an A whose CSR and CSC differ in pointers or
+ * indices, i.e. one that is not symmetric, found by one comparison on the device: GRB_INVALID_VALUE; a failed device
+ * allocation: GRB_OUT_OF_MEMORY.  In the CSR-only matrix format (GRB_SPARSE_MATRIX_FORMAT=1) the CSC IS the CSR, there is
+ * nothing to compare and the caller vouches for the symmetry (an entry whose transposed entry is missing is still found,
+ * as GRB_INVALID_VALUE). */
+typedef struct {
+  int32_t rounds;             /* filter rounds run (each reads one record back; the last of grb_ktruss drops nothing)   */
+  int32_t supports;           /* support computations run (grb_trussness: fewer than rounds)                            */
+  int64_t edges;              /* undirected edges of G                                                                 */
+  int64_t result_edges;       /* undirected edges of the result (grb_trussness: those of G)                            */
+  int32_t kmax;               /* grb_trussness: the largest k with a non-empty truss (2 when G has no edge); else the k given */
+  float   loop_ms;            /* HIP-event time of the rounds                                                          */
+} grb_truss_result;
+grb_info grb_ktruss(grb_matrix C, grb_matrix A, int k, grb_descriptor desc, grb_truss_result* result);
+grb_info grb_trussness(grb_matrix C, grb_matrix A, grb_descriptor desc, grb_truss_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
