@@ -38,6 +38,11 @@ class TrussResult(C.Structure):
                 ("kmax", C.c_int32), ("loop_ms", C.c_float)]
 
 
+class BcResult(C.Structure):
+    _fields_ = [("sources", C.c_int32), ("batches", C.c_int32), ("levels", C.c_int32), ("reached", C.c_int64),
+                ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -197,6 +202,7 @@ _SIGS = {
     "grb_tc_dense_core": [_vp, _i, _i, _i, C.POINTER(TcCoreResult)],
     "grb_ktruss": [_vp, _vp, _i, _vp, C.POINTER(TrussResult)],
     "grb_trussness": [_vp, _vp, _vp, C.POINTER(TrussResult)],
+    "grb_bc": [_vp, _vp, _vp, _i, _vp, C.POINTER(BcResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

@@ -715,6 +715,28 @@ def trussness(Cm, A, desc):
     return info, _truss_dict(res)
 
 
+def bc(v, A, sources, desc):
+    """grb_bc: v = the betweenness centrality of A's graph by batched Brandes, 64 sources per sweep.  A is n x n, f32 or
+    i32; its values are never read (stored zeros are edges), a stored A(i, j), i != j, is the edge i -> j, its diagonal
+    takes no part and its structure need not be symmetric.  sources: vertex ids (a source listed twice counts twice), or
+    None for every vertex (exact centrality).  v is an f32 vector of size n and becomes dense: v[x] = the sum over the
+    sources s of delta_s(x), not normalised and not halved (all sources on a symmetric graph count every unordered pair
+    twice, as LAGraph does), exactly 0 for a vertex between no pair.  Path counts and dependencies are f64, v is rounded
+    to f32 once; the same inputs give the same bits.  An empty list -> GrB_INVALID_VALUE; a source outside 0 .. n - 1 ->
+    GrB_INVALID_INDEX; A not square or v not of size n -> GrB_DIMENSION_MISMATCH; v not f32 or A outside f32 / i32 ->
+    GrB_NOT_IMPLEMENTED; an A without its own CSC (a product result) -> GrB_INVALID_OBJECT (v unchanged on every error).
+    Returns (info, dict(sources, batches, levels = the largest depth + 1, reached = vertices reached summed over the
+    sources, loop_ms))."""
+    res = _lib.BcResult()
+    if sources is None:
+        info = _lib.load().grb_bc(_h(v), _h(A), None, 0, _h(desc), C.byref(res))
+    else:
+        src = np.ascontiguousarray(sources, dtype=np.int32).ravel()
+        buf = src if src.size else np.zeros(1, np.int32)   # an empty list is an error of the call, not "every vertex"
+        info = _lib.load().grb_bc(_h(v), _h(A), buf.ctypes.data, int(src.size), _h(desc), C.byref(res))
+    return info, dict(sources=res.sources, batches=res.batches, levels=res.levels, reached=res.reached, loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

@@ -850,6 +850,46 @@ typedef struct {
 grb_info grb_ktruss(grb_matrix C, grb_matrix A, int k, grb_descriptor desc, grb_truss_result* result);
 grb_info grb_trussness(grb_matrix C, grb_matrix A, grb_descriptor desc, grb_truss_result* result);
 
+/* Betweenness centrality (csrc/bc.hip): batched Brandes.  The reference has no such driver (graphblas/algorithm/), so the
+ * definition is this header's own; it follows LAGraph's convention.
+ *
+ * A is n x n, f32 or i32.  Only the structure counts: stored values are never read and a stored zero is an edge.  A stored
+ * A(i, j) with i != j is the edge i -> j, the direction grb_bfs walks; diagonal entries take no part.  The graph may be
+ * directed: the structure need not be symmetric.  For a source s, sigma_s(v) is the number of shortest s -> v paths
+ * (sigma_s(s) = 1), d_s(v) is v's depth, and
+ *     delta_s(v) = sum over the edges v -> w with d_s(w) = d_s(v) + 1 of sigma_s(v) / sigma_s(w) * (1 + delta_s(w)),
+ * with delta_s(s) = 0 and delta_s(v) = 0 for a v that s does not reach.  The result is bc(v) = the sum of delta_s(v) over
+ * the sources.  No normalisation and no halving: with every vertex a source on a symmetric graph every unordered pair is
+ * counted twice, as in LAGraph.  A source listed twice counts twice.
+ *
+ * grb_bc(bc, A, sources, ns, desc, result): sources is a host array of ns vertex ids; sources == NULL means every vertex
+ * 0 .. n - 1 (exact centrality) and ns is ignored.  bc is an f32 vector of size n; it becomes dense with all n values
+ * stored, exactly 0 for a vertex between no pair.  desc may be NULL; no descriptor field is read.  result may be NULL.
+ *
+ * The same inputs give the same bits.  Path counts and dependencies are f64 on the device; bc is accumulated in f64 over
+ * all sources and rounded to f32 once, at the end.  Path counts beyond the f64 range (about 1.8e308 shortest paths between
+ * one pair) make the result undefined; LAGraph has the same limit.
+ *
+ * How: the sources are taken 64 at a time, a lane of a wave each, on n x 64 arrays of depths and path counts.  One sweep
+ * finds the depths (those grb_bfs_batch gives) and the list of vertices at every depth with the path counts right behind
+ * each level; the dependencies come back level by level.  Both are gathers in stored order without floating-point
+ * atomics.  Working memory: 16 n x 64 bytes.
+ *
+ * Every error is found before bc is written, and bc keeps what it held.  A null bc or A, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, or size(bc) != n: GRB_DIMENSION_MISMATCH; sources != NULL and ns < 1:
+ * GRB_INVALID_VALUE; a source < 0 or >= n: GRB_INVALID_INDEX (as grb_bfs_batch); bc not f32, or A not f32 / i32:
+ * GRB_NOT_IMPLEMENTED; an A without a CSC of its own (a product result): GRB_INVALID_OBJECT, as grb_ktruss; a failed
+ * device allocation: GRB_OUT_OF_MEMORY.  In the CSR-only matrix format (GRB_SPARSE_MATRIX_FORMAT=1) the CSC IS the CSR and
+ * the caller vouches for the symmetry. */
+typedef struct {
+  int32_t sources;            /* traversals run (n when sources == NULL)                                               */
+  int32_t batches;            /* sweeps of up to 64 sources                                                            */
+  int32_t levels;             /* largest depth reached by any source, + 1                                              */
+  int64_t reached;            /* vertices reached, summed over the sources (each source reaches itself)                */
+  float   loop_ms;            /* HIP-event time of all batches                                                         */
+} grb_bc_result;
+grb_info grb_bc(grb_vector bc, grb_matrix A, const grb_index* sources, int ns, grb_descriptor desc, grb_bc_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
