@@ -616,6 +616,20 @@ def bfs_set_lanes(n=-1):
     return int(_lib.load().grb_bfs_set_lanes(int(n)))
 
 
+def bfs_set_sweep_from(k=-1):
+    """grb_bfs_set_sweep_from: gathered traversals from which bfs_enqueue's groups run as one bit-parallel sweep (0: never;
+    k < 0 only queries); returns the previous value."""
+    return int(_lib.load().grb_bfs_set_sweep_from(int(k)))
+
+
+def bfs_sweep_counts():
+    """grb_bfs_sweep_counts: {"sweeps", "traversals"} -- the groups bfs_enqueue's queue has run as one sweep so far."""
+    a, b = C.c_longlong(0), C.c_longlong(0)
+    info = _lib.load().grb_bfs_sweep_counts(C.byref(a), C.byref(b))
+    assert info == 0, info
+    return {"sweeps": int(a.value), "traversals": int(b.value)}
+
+
 def bfs_set_coschedule(k=-1):
     """grb_bfs_set_coschedule: traversals per launch for bfs_enqueue (k < 1 only queries); returns the previous value."""
     return int(_lib.load().grb_bfs_set_coschedule(int(k)))

@@ -42,6 +42,8 @@ constexpr int kBatchSerial = 4;       // serial probes per lane before the wave 
 constexpr int kBatchSlots = 16;       // counter slots (spreads same-address atomics)
 constexpr int kBatchStoreMax = 16;    // level words kept for the final label pass
 constexpr int kBatchCounters = 2 + 128;   // per slot: vertices, out-degree sum, then {nf_s, mf_s} per source
+constexpr int kBatchBoxPer = kBatchCounters + 8;      // the host's box: where the light-level launch leaves TailState::cum and ::last
+constexpr int kBatchBoxWords = kBatchBoxPer + 128 + 64;
 
 typedef unsigned long long u64;
 
@@ -628,6 +630,8 @@ struct TailState {                    // zeroed by the host before every launch
   u64 slots[3][kBatchSlots * kBatchCounters];
   u64 ts[64];                         // GRB_BATCH_TRACE: wall-clock stamps of workgroup 0 (100 MHz)
   u64 dec[3][8][16];                  // what the level loop decides on: {pairs, out-edges} of a level, one line per eighth of the grid
+  u64 cum[128];                       // TailArgs::per_source: {pairs, out-edges} per source summed over the launch's levels ...
+  unsigned int last[64];              // ... and the last iteration at which the source discovered anything (0: never)
 };
 
 struct TailArgs {
@@ -641,6 +645,7 @@ struct TailArgs {
   unsigned long long edge_limit;      // leave when the next level would push more out-edges than this
   const Index* src;                   // the sweep's first level: the sources (nsrc > 0), else the words of f0 are scanned
   int nsrc;
+  int per_source;                     // the caller wants every source's own totals (the queue's sweep): box[kBatchBoxPer ..]
 };
 
 __global__ __launch_bounds__(kPThreads) void batch_tail_kernel(BatchArgs a, TailArgs t) {
@@ -916,6 +921,14 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
     block_flush(qn, cn);
     stamp();
     totals_flush_to(st->slots[j % 3], &lds, tot);          // per source: read by workgroup 0 when the launch ends, by nobody else
+    if (t.per_source)                                       // ... and summed over the levels (light levels: few sources, few pairs)
+      for (int i = threadIdx.x; i < 128; i += kPThreads) {
+        const u64 x = lds.v[2 + i];
+        if (x) {
+          atomicAdd(&st->cum[i], x);
+          if (!(i & 1)) atomicMax(&st->last[i >> 1], (unsigned int)iter);
+        }
+      }
     if (threadIdx.x < kWave) {                             // what everybody needs: the level's pairs and their out-edges
       u64 np = lds.v[2 + 2 * lane], ne = lds.v[3 + 2 * lane];
       np = wave_sum_u64(np); ne = wave_sum_u64(ne);
@@ -969,6 +982,10 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
       __hip_atomic_store(&t.box[kBatchCounters + 3], (u64)cum_pairs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&t.box[kBatchCounters + 4], (u64)status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+    if (t.per_source)
+      for (int i = threadIdx.x; i < 128 + 64; i += kPThreads)
+        __hip_atomic_store(&t.box[kBatchBoxPer + i], i < 128 ? fresh(&st->cum[i]) : (u64)fresh(&st->last[i - 128]), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(&t.box[kBatchCounters], t.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -993,9 +1010,24 @@ static int batch_big(bool in_edges) {
   return b < 64 ? 64 : b;
 }
 
+static grb_info make_slices(grb_matrix A, bool in_edges);
 static grb_info ensure_slices(grb_matrix A, bool in_edges) {
   BatchSlices& B = in_edges ? A->batch_in : A->batch_out;
   if (B.ready) return GRB_SUCCESS;
+  const grb_info i = make_slices(A, in_edges);
+  if (i != GRB_SUCCESS) {                                   // nothing half-made stays behind
+    (void)hipStreamSynchronize(ctx().stream);
+    if (B.d_slices) (void)hipFree(B.d_slices);
+    if (B.d_rows) (void)hipFree(B.d_rows);
+    if (B.d_range_off) (void)hipFree(B.d_range_off);
+    if (B.d_range_bounds) (void)hipFree(B.d_range_bounds);
+    if (B.d_range_ids) (void)hipFree(B.d_range_ids);
+    B = BatchSlices();
+  }
+  return i;
+}
+static grb_info make_slices(grb_matrix A, bool in_edges) {
+  BatchSlices& B = in_edges ? A->batch_in : A->batch_out;
   const std::vector<Index>& ptr = in_edges ? A->h_csc_ptr : A->h_csr_ptr;
   const Index n = in_edges ? A->ncols : A->nrows;
   if ((Index)ptr.size() != n + 1) return GRB_INVALID_OBJECT;
@@ -1077,36 +1109,93 @@ extern "C" long long grb_bfs_batch_set_tail(long long edges) { GRB_API_ENTER_NOI
   return before;
 }
 
-extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_index* sources, grb_descriptor desc,
-                                  grb_bfs_result* result) { GRB_API_ENTER();
-  if (!v || !A || !desc || !sources) return GRB_UNINITIALIZED_OBJECT;
-  if (k < 1 || k > 64) return GRB_INVALID_VALUE;
-  if (!A->built || !A->csr.ptr || !A->csc.ptr) return GRB_UNINITIALIZED_OBJECT;
-  if (A->nrows != A->ncols) return GRB_DIMENSION_MISMATCH;
+// ---- the sweep proper ------------------------------------------------------------------------------------------------
+// What the sweep keeps between its kernels.  grb_bfs_batch runs on the library's scratch slots (own == nullptr); the
+// sweep the traversal queue routes its gathered groups to (bfs_persist.hip) runs on buffers of its own, provisioned
+// once (bfs_sweep_provision) -- slot 7 is the one-launch traversal's pre-zeroed block, and a blocking call after a routed
+// sweep must not find it taken.
+namespace {
+struct SweepOwn {
+  void *words = nullptr, *cnt = nullptr, *src = nullptr, *tail = nullptr, *list = nullptr;
+  size_t words_cap = 0, tail_cap = 0, list_cap = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool clean_valid = false, clean[4] = {false, false, false, false};   // the rotating arrays known all-zero, for (clean_n, clean_nstore)
+  Index clean_n = 0;
+  int clean_nstore = 0;
+  bool warmed = false;                                      // every batch_* kernel has been launched once ...
+  bool warmed_own_small = false, warmed_own_wide = false;   // ... the two owner-computes instances too (they need a matrix with ranges)
+};
+SweepOwn g_sweep;
+struct SweepSizes {
+  int nstore = 1;
+  size_t words = 0, tail = 0, tail_state = 0, qcap = 0, list = 0, list_ids = 0;
+};
+struct SweepTotals {                                        // the whole sweep's, as grb_bfs_batch reports them
+  int levels = 0, last_dir = 0;
+  unsigned long long edges = 0, reached = 0;
+  bool hit_cap = false;
+  float ms = 0.f;
+};
+u64 *g_box_h = nullptr, *g_box_d = nullptr;                 // {totals, sequence number, ...}: pinned, host-coherent
+u64 g_box_seq = 0;
+}  // namespace
+
+static SweepSizes sweep_sizes(grb_matrix A) {
+  SweepSizes z;
   const Index n = A->nrows;
-  for (int s = 0; s < k; ++s) {
-    if (!v[s]) return GRB_UNINITIALIZED_OBJECT;
-    if (v[s]->dtype != GRB_F32) return GRB_DOMAIN_MISMATCH;
-    if (v[s]->nsize != n) return GRB_DIMENSION_MISMATCH;
-    if (sources[s] < 0 || sources[s] >= n) return GRB_INVALID_INDEX;
-  }
-  GRB_TRY(ctx_init());
+  // stored level words: as many as fit 1 GiB, at most kBatchStoreMax (+ the seed words) + two rotating buffers
+  z.nstore = (int)((1ull << 30) / (sizeof(u64) * (size_t)(n > 0 ? n : 1)));
+  if (z.nstore > kBatchStoreMax) z.nstore = kBatchStoreMax;
+  if (z.nstore < 1) z.nstore = 1;
+  const int nbuf = 1 + (z.nstore + 1) + 4;                  // seen, the kept levels' words, four rotating arrays
+  z.words = (size_t)nbuf * sizeof(u64) * (size_t)n + 256;
+  z.qcap = (size_t)n + (size_t)(A->nvals / kTailPiece) + 64;
+  z.tail_state = (sizeof(TailState) + 255) & ~(size_t)255;
+  z.tail = z.tail_state + 3 * sizeof(u64) * z.qcap;
+  z.list_ids = (sizeof(int) * (size_t)A->batch_out.nbig + 255) & ~(size_t)255;
+  z.list = 256 + z.list_ids + sizeof(u64) * (size_t)A->batch_out.nbig;
+  return z;
+}
+
+static grb_info batch_box() {
+  if (g_box_h) return GRB_SUCCESS;
+  GRB_HIP_TRY(hipHostMalloc((void**)&g_box_h, sizeof(u64) * kBatchBoxWords, hipHostMallocMapped | hipHostMallocCoherent));
+  memset(g_box_h, 0, sizeof(u64) * kBatchBoxWords);
+  GRB_HIP_TRY(hipHostGetDevicePointer((void**)&g_box_d, g_box_h, 0));
+  return GRB_SUCCESS;
+}
+
+// k traversals of A (both orientations, the pull hint and the slice tables ready) from sources[] into v[] under the rules
+// (mode, max_niter, switchpoint).  per != nullptr: every source's own result block, as its own one-launch traversal
+// would report it -- reached = 1 + its discoveries, edges = its out-degree + theirs, levels = the iterations its own loop
+// runs (up to and including the first that discovers nothing, at most max_niter), tight_ms = the sweep's device time / k;
+// per_dir[s] = 1 when the source's last productive level was pulled.  Timed with HIP events of its own (the library's
+// timer belongs to the caller); returns after the label pass has completed.
+static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index* sources, int rules_mode, int max_niter,
+                            float switchpoint, SweepOwn* own, grb_bfs_result* per, int* per_dir, SweepTotals* out) {
   Context& c = ctx();
   hipStream_t st = c.stream;
-  GRB_TRY(ensure_pull_hint(&A->d_pull_hint, A->csc, A->csr.ptr, st));
-  GRB_TRY(ensure_slices(A, true));
-  GRB_TRY(ensure_slices(A, false));
-
-  // stored level words: as many as fit 1 GiB, at most kBatchStoreMax (+ the seed words) + two rotating buffers
-  int nstore = (int)((1ull << 30) / (sizeof(u64) * (size_t)(n > 0 ? n : 1)));
-  if (nstore > kBatchStoreMax) nstore = kBatchStoreMax;
-  if (nstore < 1) nstore = 1;
-  const int nbuf = 1 + (nstore + 1) + 4;                    // seen, the kept levels' words, four rotating arrays
+  const Index n = A->nrows;
+  const SweepSizes z = sweep_sizes(A);
+  const int nstore = z.nstore;
   void *p_words, *p_cnt, *p_src;
-  GRB_TRY(scratch(7, (size_t)nbuf * sizeof(u64) * (size_t)n + 256, &p_words));
-  c.bfs_prezero_ptr = nullptr;                              // slot 7 is the one-launch traversal's pre-zeroed block
-  GRB_TRY(scratch(10, sizeof(u64) * kBatchSlots * kBatchCounters, &p_cnt));
-  GRB_TRY(scratch(9, sizeof(Index) * 64, &p_src));
+  static hipEvent_t s_ev0 = nullptr, s_ev1 = nullptr;
+  hipEvent_t ev0, ev1;
+  if (own) {
+    if (!own->words || own->words_cap < z.words || own->tail_cap < z.tail || own->list_cap < z.list || !own->ev0) return GRB_OUT_OF_MEMORY;
+    p_words = own->words; p_cnt = own->cnt; p_src = own->src;
+    ev0 = own->ev0; ev1 = own->ev1;
+  } else {
+    GRB_TRY(scratch(7, z.words, &p_words));
+    c.bfs_prezero_ptr = nullptr;                            // slot 7 is the one-launch traversal's pre-zeroed block
+    GRB_TRY(scratch(10, sizeof(u64) * kBatchSlots * kBatchCounters, &p_cnt));
+    GRB_TRY(scratch(9, sizeof(Index) * 64, &p_src));
+    if (!s_ev0) {
+      GRB_HIP_TRY(hipEventCreate(&s_ev0));
+      GRB_HIP_TRY(hipEventCreate(&s_ev1));
+    }
+    ev0 = s_ev0; ev1 = s_ev1;
+  }
   u64* seen = (u64*)p_words;
   // level words: slot 0 .. nstore are kept for the label pass (which level each holds is recorded as it is taken);
   // four more rotate -- a level beyond the kept ones (it labels as it discovers), the copy of `seen` a heavy push
@@ -1117,9 +1206,15 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
   // else has had the scratch slot in between
   static struct { bool valid = false; unsigned long long epoch = 0; void* ptr = nullptr; Index n = 0; int nstore = 0; bool clean[4]; } kept_pool;
   bool pool_clean[4] = {false, false, false, false};
-  if (kept_pool.valid && kept_pool.epoch + 1 == c.slot_epoch[7] && kept_pool.ptr == p_words && kept_pool.n == n && kept_pool.nstore == nstore)
-    for (int i = 0; i < 4; ++i) pool_clean[i] = kept_pool.clean[i];
-  kept_pool.valid = false;
+  if (own) {                                                // (nobody else ever has these buffers)
+    if (own->clean_valid && own->clean_n == n && own->clean_nstore == nstore)
+      for (int i = 0; i < 4; ++i) pool_clean[i] = own->clean[i];
+    own->clean_valid = false;
+  } else {
+    if (kept_pool.valid && kept_pool.epoch + 1 == c.slot_epoch[7] && kept_pool.ptr == p_words && kept_pool.n == n && kept_pool.nstore == nstore)
+      for (int i = 0; i < 4; ++i) pool_clean[i] = kept_pool.clean[i];
+    kept_pool.valid = false;
+  }
   // a rotating array other than x and y: for the light-level launch a clean one if there is one (no memset), for
   // everybody else a dirty one (so that the clean ones stay clean)
   auto pick = [&](const u64* x, const u64* y, const u64* z, bool want_clean) -> int {
@@ -1150,13 +1245,9 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
     GRB_TRY(grb_vector_set_storage(v[s], GRB_DENSE));
     a.label[s] = (float*)v[s]->d_val;
   }
-  static u64 *h_box = nullptr, *d_box = nullptr;            // {totals, sequence number}: pinned, host-coherent
-  static u64 box_seq = 0;
-  if (!h_box) {
-    GRB_HIP_TRY(hipHostMalloc((void**)&h_box, sizeof(u64) * (kBatchCounters + 8), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h_box, 0, sizeof(u64) * (kBatchCounters + 8));
-    GRB_HIP_TRY(hipHostGetDevicePointer((void**)&d_box, h_box, 0));
-  }
+  GRB_TRY(batch_box());
+  u64 *const h_box = g_box_h, *const d_box = g_box_d;
+  u64& box_seq = g_box_seq;
   GRB_HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
   GRB_HIP_TRY(hipMemsetAsync(seen, 0, 2 * sizeof(u64) * (size_t)n, st));       // seen and the seeds' words
   GRB_HIP_TRY(hipMemcpyAsync(p_src, sources, sizeof(Index) * (size_t)k, hipMemcpyHostToDevice, st));
@@ -1166,15 +1257,18 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
   // per-source frontier totals of the seed level
   unsigned long long nf_s[64], mf_s[64];
   unsigned long long edges = 0, reached = (unsigned long long)k;
+  unsigned long long reached_s[64], edges_s[64];            // per source, for `per`
+  int last_prod[64], dir_s[64];                             // the last iteration at which the source discovered anything; its direction
   for (int s = 0; s < k; ++s) {
     nf_s[s] = 1;
     mf_s[s] = (unsigned long long)(A->h_csr_ptr[(size_t)sources[s] + 1] - A->h_csr_ptr[sources[s]]);
     edges += mf_s[s];
+    reached_s[s] = 1; edges_s[s] = mf_s[s]; last_prod[s] = 0; dir_s[s] = 0;
   }
   // GRB_SPARSE_MATRIX_FORMAT = 1: no CSC storage -- the "CSC" arrays ARE the CSR arrays, and the reference's vxm
   // is forced to push whatever the mxvmode says (operations.hpp:131-133).  A pull over them would walk out-edges
   // as if they were in-edges: every source is pushed.
-  const int mode = (A->format != 0 || A->csc_alias) ? GRB_PUSHONLY : desc->desc[GRB_MXVMODE];
+  const int mode = (A->format != 0 || A->csc_alias) ? GRB_PUSHONLY : rules_mode;
   const int grid = stream_grid((long long)ceil_div(n, kWave) * kWave, kBlock);
   int iter = 1, levels = 0, last_dir = 0;
   bool any_left = true;
@@ -1196,8 +1290,8 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
     }
     return GRB_SUCCESS;
   };
-  GRB_TRY(grb_timer_start());
-  for (; iter <= desc->max_niter; ++iter) {
+  GRB_HIP_TRY(hipEventRecord(ev0, st));
+  for (; iter <= max_niter; ++iter) {
     const double t_lvl = trace ? now_us() : 0.0;
     // ---- direction per source: the reference's vertex-count rule (switchpoint) on that source's own
     // frontier, and a budget on the edges pushed in one level
@@ -1217,10 +1311,10 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
         std::sort(order, order + m, [&](int x, int y) { return mf_s[x] > mf_s[y]; });
         double pushed = 0;
         for (int i = 0; i < m; ++i)
-          if ((double)nf_s[order[i]] <= (double)desc->switchpoint * (double)n) pushed += (double)mf_s[order[i]];
+          if ((double)nf_s[order[i]] <= (double)switchpoint * (double)n) pushed += (double)mf_s[order[i]];
         for (int i = 0; i < m; ++i) {
           const int s = order[i];
-          bool pull = (double)nf_s[s] > (double)desc->switchpoint * (double)n;
+          bool pull = (double)nf_s[s] > (double)switchpoint * (double)n;
           if (!pull && pushed > budget * (double)A->nvals) { pull = true; pushed -= (double)mf_s[s]; }
           if (pull) Q |= 1ull << s; else P |= 1ull << s;
         }
@@ -1236,10 +1330,10 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
       xi[0] = pick(fcur_words, nullptr, nullptr, true);
       xi[1] = pick(fcur_words, pool[xi[0]], nullptr, true);
       xi[2] = pick(fcur_words, pool[xi[0]], pool[xi[1]], true);
-      void* p_tail;
-      const size_t qcap = (size_t)n + (size_t)(A->nvals / kTailPiece) + 64;
-      const size_t st_bytes = (sizeof(TailState) + 255) & ~(size_t)255;
-      GRB_TRY(scratch(8, st_bytes + 3 * sizeof(u64) * qcap, &p_tail));
+      void* p_tail = own ? own->tail : nullptr;
+      const size_t qcap = z.qcap;
+      const size_t st_bytes = z.tail_state;
+      if (!own) GRB_TRY(scratch(8, z.tail, &p_tail));
       TailArgs t;
       t.f0 = fcur_words;
       for (int i = 0; i < 3; ++i) t.X[i] = pool[xi[i]];
@@ -1248,10 +1342,11 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
       t.box = d_box;
       t.seq = ++box_seq;
       t.iter0 = iter;
-      t.max_niter = desc->max_niter;
+      t.max_niter = max_niter;
       t.edge_limit = (unsigned long long)tail_edges;
       t.src = (const Index*)p_src;
       t.nsrc = iter == 1 ? k : 0;
+      t.per_source = per ? 1 : 0;
       a.direct_labels = 1;
       GRB_HIP_TRY(hipMemsetAsync(p_tail, 0, st_bytes, st));
       for (int i = 0; i < 3; ++i)
@@ -1268,6 +1363,12 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
         nf_s[s] = h_box[2 + 2 * s];
         mf_s[s] = h_box[3 + 2 * s];
         if (nf_s[s]) any_left = true;
+        if (per) {
+          reached_s[s] += h_box[kBatchBoxPer + 2 * s];
+          edges_s[s] += h_box[kBatchBoxPer + 2 * s + 1];
+          const int lp = (int)h_box[kBatchBoxPer + 128 + s];
+          if (lp > last_prod[s]) { last_prod[s] = lp; dir_s[s] = 0; }
+        }
       }
       levels += done;
       last_dir = 0;
@@ -1328,9 +1429,9 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
       static const bool owner_ok = [] { const char* e = getenv("GRB_BATCH_OWNER"); return !e || atoi(e) != 0; }();
       if (B.nslices > 0 && a.prev && owner_ok && B.d_range_off) {
         // heavy level: the big rows' edges are settled by the owners of their destination ranges, in LDS
-        void* p_list;
-        const size_t list_bytes = (sizeof(int) * (size_t)B.nbig + 255) & ~(size_t)255;
-        GRB_TRY(scratch(11, 256 + list_bytes + sizeof(u64) * (size_t)B.nbig, &p_list));
+        void* p_list = own ? own->list : nullptr;
+        const size_t list_bytes = z.list_ids;
+        if (!own) GRB_TRY(scratch(11, z.list, &p_list));
         unsigned int* d_count = (unsigned int*)p_list;
         int* d_list = (int*)((char*)p_list + 256);
         u64* d_list_fw = (u64*)((char*)p_list + 256 + list_bytes);
@@ -1376,7 +1477,9 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
       pairs += nf_s[s];
       reached += nf_s[s];
       edges += mf_s[s];
-      if (nf_s[s]) any_left = true;
+      reached_s[s] += nf_s[s];
+      edges_s[s] += mf_s[s];
+      if (nf_s[s]) { any_left = true; last_prod[s] = iter; dir_s[s] = (int)((Q >> s) & 1ull); }
     }
     if (trace)
       fprintf(stderr, "batch level %d: pull %d sources, push %d (%.0f edges, %s) -> vertices %llu pairs %llu  %.1f us\n",
@@ -1384,7 +1487,7 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
               pairs, now_us() - t_lvl);
     if (!any_left) break;
   }
-  const bool hit_cap = iter > desc->max_niter && any_left;
+  const bool hit_cap = iter > max_niter && any_left;
   // ---- the depth vectors
   {
     LabelArgs L;
@@ -1394,7 +1497,7 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
     for (int i = 0; i <= kBatchStoreMax; ++i) {
       L.W[i] = i < nkept ? kept_words[i] : nullptr;
       // discovered by the last allowed iteration: never assigned (bfs.hpp:48-66)
-      L.lab[i] = i < nkept && kept_level[i] + 1 <= desc->max_niter ? (float)(kept_level[i] + 1) : 0.f;
+      L.lab[i] = i < nkept && kept_level[i] + 1 <= max_niter ? (float)(kept_level[i] + 1) : 0.f;
     }
     for (int s = 0; s < 64; ++s) L.label[s] = a.label[s];
     hipLaunchKernelGGL(batch_labels_kernel, dim3(grid), dim3(kBlock), 0, st, L);
@@ -1403,22 +1506,232 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
   if (hit_cap && any_direct) {
     // vertices discovered by the last allowed iteration are never assigned by the reference loop (bfs.hpp:48-66)
     hipLaunchKernelGGL(batch_unlabel_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, a,
-                       (float)(desc->max_niter + 1));
+                       (float)(max_niter + 1));
     GRB_HIP_TRY(hipGetLastError());
   }
-  GRB_TRY(grb_timer_stop(&ms));
-  kept_pool.valid = true;
-  kept_pool.epoch = c.slot_epoch[7];
-  kept_pool.ptr = p_words;
-  kept_pool.n = n;
-  kept_pool.nstore = nstore;
-  for (int i = 0; i < 4; ++i) kept_pool.clean[i] = pool_clean[i];
-  desc->lastmxv = last_dir ? GRB_PULLONLY : GRB_PUSHONLY;
+  GRB_HIP_TRY(hipEventRecord(ev1, st));
+  GRB_HIP_TRY(hipEventSynchronize(ev1));                    // the labels are in place
+  GRB_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  if (own) {
+    own->clean_valid = true;
+    own->clean_n = n;
+    own->clean_nstore = nstore;
+    for (int i = 0; i < 4; ++i) own->clean[i] = pool_clean[i];
+  } else {
+    kept_pool.valid = true;
+    kept_pool.epoch = c.slot_epoch[7];
+    kept_pool.ptr = p_words;
+    kept_pool.n = n;
+    kept_pool.nstore = nstore;
+    for (int i = 0; i < 4; ++i) kept_pool.clean[i] = pool_clean[i];
+  }
+  if (per)
+    for (int s = 0; s < k; ++s) {
+      const int lv = last_prod[s] + 1;
+      per[s].levels = lv < max_niter ? lv : max_niter;
+      per[s].tight_ms = ms / (float)k;
+      per[s].edges_traversed = (int64_t)edges_s[s];
+      per[s].reached = (int32_t)(reached_s[s] > 0x7fffffffull ? 0x7fffffff : reached_s[s]);
+      if (per_dir) per_dir[s] = dir_s[s];
+    }
+  out->levels = levels; out->last_dir = last_dir; out->edges = edges; out->reached = reached; out->hit_cap = hit_cap; out->ms = ms;
+  return GRB_SUCCESS;
+}
+
+// ---- the sweep as the traversal queue uses it (bfs_persist.hip: bfs_co_flush) ------------------------------------------
+// Every batch_* kernel launched once on nothing (n = 0, no slices, an empty list), so that no sweep pays a kernel's first
+// launch: the code object is loaded by the first, the others are looked up.  The owner-computes kernels run over the
+// matrix's real ranges with an empty list of big rows (they clear their LDS and find nothing to write back).
+static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
+  Context& c = ctx();
+  hipStream_t st = c.stream;
+  GRB_TRY(batch_box());
+  BatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.optr = A->csr.ptr; a.oind = A->csr.ind; a.iptr = A->csc.ptr; a.iind = A->csc.ind;
+  a.hint = A->d_pull_hint;
+  a.n = 0;
+  a.seen = (u64*)own->words; a.fcur = (const u64*)own->words; a.fnext = (u64*)own->words;
+  a.big = batch_big(true);
+  a.counters = (u64*)own->cnt;
+  a.direct_labels = 1;
+  GRB_HIP_TRY(hipMemsetAsync(own->cnt, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
+  GRB_HIP_TRY(hipMemsetAsync(own->list, 0, 256, st));       // the list's length: 0
+  unsigned int* d_count = (unsigned int*)own->list;
+  int* d_list = (int*)((char*)own->list + 256);
+  u64* d_list_fw = (u64*)((char*)own->list + 256 + z.list_ids);
+  if (!own->warmed) {
+    hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, a.seen, a.seen, (const Index*)own->src, 0);
+    hipLaunchKernelGGL(batch_pull_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_pull_slices_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_big_apply_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_push_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_push_slices_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_big_list_kernel, dim3(1), dim3(kBlock), 0, st, a, d_list, d_list_fw, d_count);
+    hipLaunchKernelGGL(batch_push_commit_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_unlabel_kernel, dim3(1), dim3(kBlock), 0, st, a, 0.f);
+    LabelArgs L;
+    memset(&L, 0, sizeof(L));
+    L.seen = a.seen;
+    hipLaunchKernelGGL(batch_labels_kernel, dim3(1), dim3(kBlock), 0, st, L);
+    GRB_HIP_TRY(hipGetLastError());
+    // the light-level launch on an empty queue: one level that finds nothing, the grid barrier at its real width
+    TailArgs t;
+    memset(&t, 0, sizeof(t));
+    t.f0 = a.fcur;
+    for (int i = 0; i < 3; ++i) {
+      t.X[i] = a.seen;
+      t.queue[i] = (u64*)((char*)own->tail + z.tail_state) + (size_t)i * z.qcap;
+    }
+    t.st = (TailState*)own->tail;
+    t.box = g_box_d;
+    t.seq = ++g_box_seq;
+    t.iter0 = 1; t.max_niter = 1;
+    t.src = (const Index*)own->src;
+    t.per_source = 1;
+    GRB_HIP_TRY(hipMemsetAsync(own->tail, 0, z.tail_state, st));
+    hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
+    GRB_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, g_box_d, ++g_box_seq);
+    GRB_HIP_TRY(hipGetLastError());
+  }
+  // one workgroup of each owner-computes instance, once per process, on the first matrix that has such ranges
+  const BatchSlices& B = A->batch_out;
+  if (B.d_range_off && B.nranges > 0) {
+    a.nbig = B.nbig;
+    if (B.nsmall > 0 && !own->warmed_own_small) {
+      hipLaunchKernelGGL((batch_push_owner_kernel<kOwnSmallRows, 512>), dim3(1), dim3(512), 0, st, a, (const Index*)B.d_range_off,
+                         B.nranges, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                         (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
+      own->warmed_own_small = true;
+    }
+    if (B.nranges > B.nsmall && !own->warmed_own_wide) {
+      hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(1), dim3(1024), 0, st, a,
+                         (const Index*)B.d_range_off, B.nranges, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                         (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + B.nsmall);
+      own->warmed_own_wide = true;
+    }
+    GRB_HIP_TRY(hipGetLastError());
+  }
+  GRB_HIP_TRY(hipStreamSynchronize(st));
+  if (__atomic_load_n(&g_box_h[kBatchCounters], __ATOMIC_ACQUIRE) != g_box_seq) return GRB_PANIC;
+  own->warmed = true;
+  return GRB_SUCCESS;
+}
+
+static grb_info sweep_grow(void** p, size_t* cap, size_t bytes) {
+  if (*cap >= bytes) return GRB_SUCCESS;
+  if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+  const size_t want = (bytes + bytes / 8 + 255) & ~(size_t)255;
+  GRB_HIP_TRY(hipMalloc(p, want));
+  *cap = want;
+  return GRB_SUCCESS;
+}
+
+// Once per matrix, at its first gathered launch under the width rule: the slice and owner-range tables of both orientations, the
+// sweep's own buffers (kept from matrix to matrix, grown for a larger one; new memory within a quarter of what the device
+// has free) and the first launch of its kernels.  A->sweep_state: 1 the queue may sweep this matrix, -1 it may not.
+// The attempt is made once: whatever stops it -- the memory rule at that moment included -- leaves the route off for this
+// matrix until it is built again (a retry at every launch would put an allocation attempt in front of every traversal).
+grb_info grb::bfs_sweep_provision(grb_matrix A) {
+  if (A->sweep_state != 0) return A->sweep_state > 0 ? GRB_SUCCESS : GRB_NOT_IMPLEMENTED;
+  A->sweep_state = -1;
+  if (A->format != 0 || A->csc_alias || !A->csr.ptr || !A->csc.ptr || A->nrows != A->ncols || A->nrows < 1) return GRB_NOT_IMPLEMENTED;
+  if ((Index)A->h_csr_ptr.size() != A->nrows + 1 || (Index)A->h_csc_ptr.size() != A->nrows + 1) return GRB_NOT_IMPLEMENTED;
+  auto failed = [](grb_info i) { (void)hipGetLastError(); return i; };
+  Context& c = ctx();
+  SweepOwn& o = g_sweep;
+  // the memory rule first, over everything this call may allocate: the tables of an orientation that has none yet by
+  // their upper bounds (at most nvals / big rows, a slice per kBatchPushSlice entries and per row, the owner offsets
+  // capped at 128 Mi entries as ensure_slices caps them), then the buffers by their sizes
+  size_t grow = 0, list_bound = sweep_sizes(A).list;
+  for (int in = 0; in < 2; ++in) {
+    if ((in ? A->batch_in : A->batch_out).ready) continue;
+    const size_t max_rows = (size_t)(A->nvals / batch_big(in != 0)) + 1;
+    const size_t max_slices = (size_t)(A->nvals / (in ? kBatchSlice : kBatchPushSlice)) + max_rows;
+    grow += sizeof(int4) * max_slices + sizeof(Index) * max_rows;
+    if (!in) {
+      list_bound = 256 + ((sizeof(int) * max_rows + 255) & ~(size_t)255) + sizeof(u64) * max_rows;   // (the big-row list: SweepSizes::list)
+      const size_t max_ranges = (size_t)(3 * 256 + A->nrows / kOwnSmallRows + 2);
+      grow += sizeof(Index) * std::min<size_t>(max_rows * (max_ranges + 1), (size_t)128 << 20) + 2 * sizeof(Index) * (max_ranges + 1);
+    }
+  }
+  {
+    const SweepSizes zb = sweep_sizes(A);
+    if (o.words_cap < zb.words) grow += zb.words + zb.words / 8;
+    if (o.tail_cap < zb.tail) grow += zb.tail + zb.tail / 8;
+    if (o.list_cap < list_bound) grow += list_bound + list_bound / 8;
+  }
+  if (grow > 0) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
+    if (grow + 4096 > free_b / 4) return GRB_OUT_OF_MEMORY;
+  }
+  grb_info i = ensure_pull_hint(&A->d_pull_hint, A->csc, A->csr.ptr, c.stream);
+  if (i == GRB_SUCCESS) i = ensure_slices(A, true);
+  if (i == GRB_SUCCESS) i = ensure_slices(A, false);
+  if (i != GRB_SUCCESS) return failed(i);
+  const SweepSizes z = sweep_sizes(A);
+  if (o.words_cap < z.words || o.tail_cap < z.tail || o.list_cap < z.list) {
+    if (hipStreamSynchronize(c.stream) != hipSuccess) return failed(GRB_PANIC);   // (an earlier sweep may still read the old ones)
+    o.clean_valid = false;
+    i = sweep_grow(&o.words, &o.words_cap, z.words);
+    if (i == GRB_SUCCESS) i = sweep_grow(&o.tail, &o.tail_cap, z.tail);
+    if (i == GRB_SUCCESS) i = sweep_grow(&o.list, &o.list_cap, z.list);
+    if (i != GRB_SUCCESS) return failed(i);
+  }
+  if (!o.cnt) {
+    if (hipMalloc(&o.cnt, sizeof(u64) * kBatchSlots * kBatchCounters) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
+    if (hipMalloc(&o.src, 256) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
+    if (hipMemset(o.src, 0, 256) != hipSuccess) return failed(GRB_PANIC);
+  }
+  if (!o.ev0) {
+    if (hipEventCreate(&o.ev0) != hipSuccess || hipEventCreate(&o.ev1) != hipSuccess) return failed(GRB_PANIC);
+  }
+  i = sweep_warm(A, &o, z);
+  if (i != GRB_SUCCESS) return failed(i);
+  A->sweep_state = 1;
+  return GRB_SUCCESS;
+}
+
+// k (2 .. 64) queued traversals of a provisioned matrix as one sweep on the sweep's own buffers; per[s] and per_dir[s] as
+// batch_sweep leaves them.  Anything but GRB_SUCCESS: the vectors hold nothing to rely on, the caller runs the traversals
+// some other way.
+grb_info grb::bfs_sweep_routed(grb_vector* v, int k, grb_matrix A, const grb_index* sources, int mode, int max_niter, float switchpoint,
+                               grb_bfs_result* per, int* per_dir) {
+  if (k < 1 || k > 64 || A->sweep_state != 1) return GRB_NOT_IMPLEMENTED;
+  SweepTotals tot;
+  const grb_info i = batch_sweep(v, k, A, sources, mode, max_niter, switchpoint, &g_sweep, per, per_dir, &tot);
+  if (i != GRB_SUCCESS) { g_sweep.clean_valid = false; return i; }
+  return tot.hit_cap ? GRB_NOT_IMPLEMENTED : GRB_SUCCESS;
+}
+
+extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_index* sources, grb_descriptor desc,
+                                  grb_bfs_result* result) { GRB_API_ENTER();
+  if (!v || !A || !desc || !sources) return GRB_UNINITIALIZED_OBJECT;
+  if (k < 1 || k > 64) return GRB_INVALID_VALUE;
+  if (!A->built || !A->csr.ptr || !A->csc.ptr) return GRB_UNINITIALIZED_OBJECT;
+  if (A->nrows != A->ncols) return GRB_DIMENSION_MISMATCH;
+  const Index n = A->nrows;
+  for (int s = 0; s < k; ++s) {
+    if (!v[s]) return GRB_UNINITIALIZED_OBJECT;
+    if (v[s]->dtype != GRB_F32) return GRB_DOMAIN_MISMATCH;
+    if (v[s]->nsize != n) return GRB_DIMENSION_MISMATCH;
+    if (sources[s] < 0 || sources[s] >= n) return GRB_INVALID_INDEX;
+  }
+  GRB_TRY(ctx_init());
+  hipStream_t st = ctx().stream;
+  GRB_TRY(ensure_pull_hint(&A->d_pull_hint, A->csc, A->csr.ptr, st));
+  GRB_TRY(ensure_slices(A, true));
+  GRB_TRY(ensure_slices(A, false));
+  SweepTotals tot;
+  GRB_TRY(batch_sweep(v, k, A, sources, desc->desc[GRB_MXVMODE], desc->max_niter, desc->switchpoint, nullptr, nullptr, nullptr, &tot));
+  desc->lastmxv = tot.last_dir ? GRB_PULLONLY : GRB_PUSHONLY;
   if (result) {
-    result->levels = levels;
-    result->tight_ms = ms;
-    result->edges_traversed = hit_cap ? -1 : (int64_t)edges;   // under a cap the tally would count unassigned vertices
-    result->reached = hit_cap ? -1 : (int32_t)(reached > 0x7fffffffull ? 0x7fffffff : reached);
+    result->levels = tot.levels;
+    result->tight_ms = tot.ms;
+    result->edges_traversed = tot.hit_cap ? -1 : (int64_t)tot.edges;   // under a cap the tally would count unassigned vertices
+    result->reached = tot.hit_cap ? -1 : (int32_t)(tot.reached > 0x7fffffffull ? 0x7fffffff : tot.reached);
   }
   return GRB_SUCCESS;
 }

@@ -175,9 +175,15 @@ extern "C" grb_info grb_bfs_wait(grb_bfs_ticket ticket, grb_bfs_result* result) 
   }
   if (state == 3) {                                         // still waiting for its co-scheduled launch to fill: launch what there is
     GRB_TRY(bfs_co_flush());
-    if (bfs_ticket_state(slot, seq, nullptr, nullptr, nullptr, nullptr, nullptr) == 4) {
+    const int after = bfs_ticket_state(slot, seq, nullptr, nullptr, nullptr, nullptr, &parked);
+    if (after == 4) {
       bfs_ticket_release(slot);                             // the launch was refused: the same traversal, now
       return grb_bfs_fused(v, A, source, desc, result, nullptr, 0, 0);
+    }
+    if (after == 2) {                                       // the group ran as one sweep: its result is parked
+      if (result) *result = parked;
+      bfs_ticket_release(slot);
+      return GRB_SUCCESS;
     }
   } else if (state == 4) {
     bfs_ticket_release(slot);
@@ -217,6 +223,20 @@ extern "C" int grb_bfs_set_lanes(int n) { GRB_API_ENTER_NOINFO();
 // side in one grid (bfs_persist.hip: bfs_co_kernel).  k < 1 only queries.  Returns the previous value.
 extern "C" int grb_bfs_set_coschedule(int k) { grb::ApiScope api_scope__; (void)api_scope__.enter(false, false);   // (one of the queue's own)
   return bfs_co_setting(k);
+}
+
+// Gathered traversals from which the queue runs a group as one bit-parallel sweep (under the default width rule): 0 turns
+// the route off, k < 0 only queries.  Returns the previous value.
+extern "C" int grb_bfs_set_sweep_from(int k) { grb::ApiScope api_scope__; (void)api_scope__.enter(false, false);   // (one of the queue's own)
+  return bfs_sweep_from_setting(k);
+}
+
+// Groups the queue has run as a sweep since the process began, and the traversals they carried (what has gathered is
+// launched first).
+extern "C" grb_info grb_bfs_sweep_counts(long long* sweeps, long long* traversals) { GRB_API_ENTER_BFSQ();
+  GRB_TRY(bfs_co_flush());
+  bfs_sweep_counts(sweeps, traversals);
+  return GRB_SUCCESS;
 }
 
 // Measurement passes: HIP events (on the library's stream) around the launches of several traversals.  on != 0 starts

@@ -1023,6 +1023,13 @@ incl = (int)wave_incl_scan_u32((unsigned)incl);
 #endif
 constexpr int kCoMax = GRB_CO_MAX;            // sub-grids per launch at most (two waves each on a CU: GRB_CO_LEAN_WPE x 4 / 2)
 constexpr int kCoTrain = 48;
+// Gathered traversals from which the queue runs the group as one bit-parallel sweep instead of the co-scheduled launch:
+// the smallest K of the table in docs/experiments.md R8.1 from which the sweep measured faster at that K and every larger
+// one, by more than the co-scheduled launch's run-to-run spread (RMAT-22: 0.0557 against 0.0546 at 20, 0.0488 against 0.0587 ms per
+// traversal at 24, 0.0297 against 0.0525 at 48 -- a sweep costs about 0.65 ms plus 16 us per source).
+#ifndef GRB_BFS_SWEEP_FROM
+#define GRB_BFS_SWEEP_FROM 24
+#endif
 struct LaunchArgs {
   PersistArgs a;
   GridArgs g[kCoMax];
@@ -1344,6 +1351,9 @@ struct CoPend {                                  // a traversal that has its tic
 struct BfsRing {
   int co_width = 0;                              // traversals per launch (grb_bfs_set_coschedule): 0 (the default) the width rule
                                                  // (co_grids) picks it; 1 every traversal its own launch; k fixed
+  int sweep_from = GRB_BFS_SWEEP_FROM;           // under the width rule a gathered group of this many plain traversals or more
+                                                 // runs as ONE bit-parallel sweep (bfs_batch.hip); 0: never (grb_bfs_set_sweep_from)
+  long long sweeps = 0, sweep_trav = 0;          // groups that ran as a sweep since the process began, and their traversals
   int co_n = 0;                                  // ... and the ones that wait for the launch to fill (ticket state 3)
   CoPend co[kCoTrain];
   BfsLane lane[kMaxLanes + 1 + kCoMax];          // [0]: the library's stream (blocking calls, one lane); [1 ..]: the lanes proper;
@@ -1874,6 +1884,62 @@ static grb_info bfs_co_launch(int ntrav, const CoPend* pend, int width, int g_mu
   return GRB_SUCCESS;
 }
 
+// A gathered group as ONE sweep of the batched traversal (bfs_batch.hip): one 64-bit word per vertex, so a gather per
+// edge serves every source, where the co-scheduled launch reads the hint, the row pointers and the lists once per
+// traversal.  Under the width rule only (an explicit width or lanes ask for per-traversal kernels), for plain traversals
+// (push-pull, no iteration cap below the default) of a matrix the sweep is provisioned for.  The sweep runs here, on the
+// library's stream, and its results are parked in the tickets once its label pass has completed; GRB_NOT_IMPLEMENTED
+// (or whatever the sweep returned, the HIP error cleared): the caller launches the group the usual way.
+static grb_info bfs_co_sweep(int ntrav, const CoPend* pend) {
+  Context& c = ctx();
+  if (g_ring.co_width != 0 || g_ring.lanes != 1 || g_ring.sweep_from < 1 || ntrav < 2 || ntrav > 64) return GRB_NOT_IMPLEMENTED;
+  static const bool force_fallback = [] { const char* e = getenv("GRB_BFS_FORCE_FALLBACK"); return e && atoi(e) != 0; }();
+  if (force_fallback) return GRB_NOT_IMPLEMENTED;
+  grb_matrix A = pend[0].A;
+  const BfsRules& r = pend[0].rules;
+  if (r.mode != GRB_PUSHPULL || r.max_niter < kDefaultMaxNiter) return GRB_NOT_IMPLEMENTED;   // (rules no group is swept under)
+  // A's first gathered launch provisions the sweep, whatever the group's size: a caller's warm-up group may be smaller
+  // than the groups that follow, and those must find nothing left to make.  (Not the first one-traversal launch, where
+  // the twelve sub-grids are provisioned: a caller who only ever makes blocking calls would pay the sweep's tables and
+  // 22 words per vertex for nothing.)
+  if (bfs_sweep_provision(A) != GRB_SUCCESS || ntrav < g_ring.sweep_from) return GRB_NOT_IMPLEMENTED;
+  grb_vector v[kCoTrain];
+  grb_index src[kCoTrain];
+  grb_bfs_result per[kCoTrain];
+  int dir[kCoTrain];
+  for (int i = 0; i < ntrav; ++i) {
+    if (pend[i].A != A || !(pend[i].rules == r) || pend[i].v->dtype != GRB_F32) return GRB_NOT_IMPLEMENTED;
+    v[i] = pend[i].v; src[i] = pend[i].source;
+  }
+  GRB_TRY(bfs_lanes_fence(c.stream));
+  if (g_ring.co_profile) {
+    if (!g_ring.co_ev) g_ring.co_ev = new std::vector<hipEvent_t>();
+    while (g_ring.co_ev->size() < g_ring.co_ev_used + 2) {
+      hipEvent_t e;
+      GRB_HIP_TRY(hipEventCreate(&e));
+      g_ring.co_ev->push_back(e);
+    }
+    GRB_HIP_TRY(hipEventRecord((*g_ring.co_ev)[g_ring.co_ev_used], c.stream));
+  }
+  const grb_info si = bfs_sweep_routed(v, ntrav, A, src, r.mode, r.max_niter, r.switchpoint, per, dir);
+  if (si != GRB_SUCCESS) { (void)hipGetLastError(); return si; }
+  if (g_ring.co_profile) {
+    GRB_HIP_TRY(hipEventRecord((*g_ring.co_ev)[g_ring.co_ev_used + 1], c.stream));
+    g_ring.co_ev_used += 2;
+    g_ring.co_prof_trav += ntrav;
+  }
+  ++g_ring.sweeps;
+  g_ring.sweep_trav += ntrav;
+  for (int i = 0; i < ntrav; ++i) {
+    BfsTicket& t = g_ring.t[pend[i].slot];
+    t.res = per[i];
+    t.state = 2;                                            // complete: the wait hands the parked block out
+    pend[i].v->d_nnz = (Index)per[i].reached;
+    pend[i].desc->lastmxv = dir[i] ? GRB_PULLONLY : GRB_PUSHONLY;
+  }
+  return GRB_SUCCESS;
+}
+
 // Waits for the record of a queued traversal and unpacks it.
 static grb_info bfs_persistent_collect(int slot, int seq, int profile, void* p_rec, unsigned long long* trace,
                                        grb_bfs_level* levels_out, int max_levels, int* levels, int* last_dir,
@@ -2013,6 +2079,7 @@ grb_info grb::bfs_co_flush() {
   // whose 512-thread instance fits m per CU, -DGRB_CO_LEAN_FROM=512; tools/bfs_single_wide_probe.py.  Three per CU, 24
   // waves, measured 0.111 ms against 0.098 for the 1024-thread kernel: one traversal is not short of waves)
   static const int single_wide = getenv("GRB_BFS_SINGLE_WIDE") ? atoi(getenv("GRB_BFS_SINGLE_WIDE")) : 0;
+  if (k >= 2 && bfs_co_sweep(k, pend) == GRB_SUCCESS) return GRB_SUCCESS;   // (the tickets hold the results)
   if (k >= 2) li = bfs_co_launch(k, pend, g_ring.co_width);
   else if (single_wide > 1) li = bfs_co_launch(1, pend, 1, single_wide);
   if (li == GRB_SUCCESS) {
@@ -2068,6 +2135,20 @@ int grb::bfs_co_setting(int set) {
     g_ring.co_width = set > kCoMax ? kCoMax : set;
   }
   return before;
+}
+// Gathered traversals from which the queue sweeps (0: never).  What has gathered so far is launched first.  Returns the
+// previous value; set < 0 only queries.
+int grb::bfs_sweep_from_setting(int set) {
+  const int before = g_ring.sweep_from;
+  if (set >= 0 && set != before) {
+    (void)bfs_co_flush();
+    g_ring.sweep_from = set;
+  }
+  return before;
+}
+void grb::bfs_sweep_counts(long long* sweeps, long long* traversals) {
+  if (sweeps) *sweeps = g_ring.sweeps;
+  if (traversals) *traversals = g_ring.sweep_trav;
 }
 // Traversals in flight at once (1 .. 8): n lanes of num_cu / n workgroups each.  Everything queued so far is waited for
 // first (a launch needs its whole grid resident: lanes of different widths must not meet).  Returns the previous value.

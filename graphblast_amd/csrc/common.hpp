@@ -606,6 +606,7 @@ struct grb_vector_s {
 };
 
 namespace grb {
+constexpr int kDefaultMaxNiter = 10000;          // grb_descriptor_load_defaults (util.hpp:39-132); a traversal under it is capped
 // rows of >= 4096 entries cut into 4096-entry slices for the batched traversal (bfs_batch.hip)
 struct BatchSlices {
   bool ready = false;
@@ -698,6 +699,7 @@ struct grb_matrix_s {
   int* d_oc2_bigidx = nullptr;
   int oc2_nb = 0, oc2_nrows = 0, oc2_state = 0, oc2_grid = 0;
   grb::BatchSlices batch_in, batch_out;          // bfs_batch.hip, built lazily
+  int sweep_state = 0;                           // the queue's sweep (bfs_sweep_provision): 0 not tried, 1 provisioned, -1 not for this matrix
   void* tc_prep = nullptr;                       // tc_count.hip: the degree-oriented lists of a lower triangle (built by the first count)
 };
 
@@ -848,6 +850,12 @@ int bfs_lanes_setting(int set);                  // traversals in flight at once
 int bfs_co_setting(int set);                     // traversals per launch (grb_bfs_set_coschedule); set < 1 only queries
 grb_info bfs_co_profile(int on, double* ms_total, int* launches, int* traversals);   // HIP events around those launches
 bool bfs_co_pending();                           // traversals that have a ticket and no launch yet
+// bfs_batch.hip: the bit-parallel sweep as the queue uses it for a gathered group (bfs_persist.hip: bfs_co_flush)
+grb_info bfs_sweep_provision(grb_matrix A);      // once per matrix: tables, the sweep's own buffers, its kernels' first launch
+grb_info bfs_sweep_routed(grb_vector* v, int k, grb_matrix A, const grb_index* sources, int mode, int max_niter, float switchpoint,
+                          grb_bfs_result* per, int* per_dir);
+void bfs_sweep_counts(long long* sweeps, long long* traversals);   // groups the queue has swept so far, and their traversals
+int bfs_sweep_from_setting(int set);             // gathered traversals from which the queue sweeps (0: never); set < 0 only queries
 grb_info bfs_co_flush();                         // ... launched now (every entry point but the queue's own does this first)
 grb_info bfs_lanes_fence(hipStream_t s);         // s waits for what the lanes have in flight (before a whole-device grid)
 void bfs_lanes_unfence();                        // the lanes' next launches wait for the library's stream again

@@ -310,7 +310,7 @@ static grb_info desc_apply_modes(grb_descriptor d) {
 // parseArgs defaults, graphblas/util.hpp:39-132
 grb_info grb_descriptor_load_defaults(grb_descriptor d) { GRB_API_ENTER();
   if (!d) return GRB_UNINITIALIZED_OBJECT;
-  d->niter = 10; d->max_niter = 10000; d->directed = 0; d->timing = 1; d->transpose = 0;
+  d->niter = 10; d->max_niter = grb::kDefaultMaxNiter; d->directed = 0; d->timing = 1; d->transpose = 0;
   d->mxvmode = 1; d->switchpoint = 0.01f; d->dirinfo = 0; d->struconly = 0; d->opreuse = 0;
   d->memusage = 1.0f; d->endbit = 1; d->sort = 1; d->atomic = 0; d->earlyexit = 1; d->fusedmask = 1;
   d->nthread = 128; d->debug = 0; d->edgeswitch = 0.f;
@@ -844,6 +844,7 @@ void grb::matrix_release_device(grb_matrix A) {
     if (b->d_range_ids) (void)hipFree(b->d_range_ids);
     *b = BatchSlices();
   }
+  A->sweep_state = 0;
   A->nonneg_values = -1; A->mean_value = -1.0; A->small_int_values = -1;
   tc_prep_free(A);
   free_spmv_plan(&A->plan_csr);

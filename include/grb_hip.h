@@ -499,7 +499,8 @@ grb_info grb_bfs_fused(grb_vector v, grb_matrix A, grb_index source, grb_descrip
  * desc must stay alive and untouched by the caller until the ticket has been waited for (v's contents are undefined
  * until then; any other entry point may be called meanwhile -- it is ordered behind the queued traversals on the
  * stream).  Under co-scheduling (the default) a queued traversal starts on the device when a ticket is waited for or
- * another entry point is called, not at the enqueue (see grb_bfs_set_coschedule).  At most
+ * another entry point is called, not at the enqueue (see grb_bfs_set_coschedule); a gathered group of
+ * 24 or more plain traversals runs as one bit-parallel sweep inside that call (see grb_bfs_set_sweep_from).  At most
  * 256 tickets may be outstanding (GRB_INSUFFICIENT_SPACE).  A traversal the one-launch kernel does not serve (road-network
  * queues, GRB_SPARSE_MATRIX_FORMAT=1) runs to its end inside the enqueue call; its ticket waits like any other.
  * grb_bfs_wait returns what grb_bfs_fused would have returned (a launch that could not finish is re-run through the
@@ -544,6 +545,25 @@ int grb_bfs_set_lanes(int n);
  * (a caller who restores what a query returned gets one traversal per launch).  (No counterpart in the reference, whose loop
  * is one traversal with several host round trips per level: algorithm/bfs.hpp:42-88.) */
 int grb_bfs_set_coschedule(int k);
+/* Gathered traversals that run as ONE bit-parallel sweep.  Under the default width rule (no grb_bfs_set_coschedule, one
+ * lane) a gathered group of k >= 24 traversals of one matrix (docs/experiments.md R8.1) runs as one sweep of the
+ * batched traversal (grb_bfs_batch's: one 64-bit word per vertex, so one gather per edge serves every source) when the
+ * matrix has both orientations and every traversal of the group is plain: GRB_PUSHPULL, max_niter not below the
+ * descriptor's default, f32 vectors, one set of rules.  Everything else takes the co-scheduled launch, as does a sweep
+ * that fails (out of memory, a barrier that gave up): nothing is reported, the group is launched the usual way.  The
+ * sweep runs where the launch would have gone out (a wait, another entry point, another matrix or rules, 48 gathered),
+ * to its end: the tickets hold their results when that call returns, parked only after the label pass has completed.
+ * Labels and result blocks are those of grb_bfs_fused per source (levels, reached, edges_traversed; tight_ms is the
+ * sweep's device time divided by k); desc's lastmxv is the last traversal's.  The sweep keeps buffers of its own, 22
+ * 64-bit words per vertex plus its queues (about 0.85 GB at RMAT-22; kept from matrix to matrix and grown for a larger
+ * one), provisioned within a quarter of the free device memory by the matrix's first gathered launch, of any size (one attempt per matrix: a matrix they cannot be made for then is not swept until it is built
+ * again).  grb_bfs_set_sweep_from(k) sets the group
+ * size from which the queue sweeps (0: never -- grb_bfs_set_coschedule(k >= 1) and grb_bfs_set_lanes(n > 1) also keep
+ * every traversal on the per-traversal kernels); k < 0 only queries.  Returns the previous value. */
+int grb_bfs_set_sweep_from(int k);
+/* Groups the queue has run as a sweep since the process began and the traversals they carried (what has gathered is
+ * launched first); either pointer may be NULL. */
+grb_info grb_bfs_sweep_counts(long long* sweeps, long long* traversals);
 /* Measurement: HIP events on the library's stream around every launch of several traversals.  on != 0 starts collecting
  * (what has gathered is launched first); on == 0 stops, waits for the launches and reports their summed duration, their
  * number and the traversals they ran (bench.py's roofline block of the co-scheduled sibling). */
