@@ -30,7 +30,9 @@
 //                    The vectors are what k calls of algorithm::bfs return: BFS depth is unique.
 #include "bfs_kernels.hpp"
 #include "persist_common.hpp"
+#include "batch_decide.hpp"
 #include <chrono>
+#include <climits>
 
 namespace grb {
 
@@ -41,8 +43,15 @@ constexpr int kBatchPushSlice = 1024; // push: out-edge slices (every edge is a 
 constexpr int kBatchSerial = 4;       // serial probes per lane before the wave takes over
 constexpr int kBatchSlots = 16;       // counter slots (spreads same-address atomics)
 constexpr int kBatchStoreMax = 16;    // level words kept for the final label pass
-constexpr int kBatchCounters = 2 + 128;   // per slot: vertices, out-degree sum, then {nf_s, mf_s} per source
+constexpr int kBatchCounters = 2 + 128 + 1;   // per slot: vertices, the big in-rows still open (below), {nf_s, mf_s} per source, big out-rows found
+constexpr int kCntInOpen = 1, kCntBigOut = 2 + 128;
 constexpr int kBatchBoxPer = kBatchCounters + 8;      // the host's box: where the light-level launch leaves TailState::cum and ::last
+constexpr int kBoxDecision = kBatchCounters + 5;      // box: {qmask, pmask, kind} of the NEXT level, as batch_totals_kernel decided it
+constexpr int kBatchCtlWords = 4;                     // the device's copy of the same three, behind the counter slots
+// counter kCntInOpen: the big in-rows that still lack a bit of some source (fewer than 2^31: a row index is an int), with
+// bit 62 set when the level's batch_big_apply_kernel counted them at all; counter kCntBigOut: the vertices with a new bit
+// whose out-row is big
+constexpr unsigned long long kInOpenCounted = 1ull << 62;
 constexpr int kBatchBoxWords = kBatchBoxPer + 128 + 64;
 
 typedef unsigned long long u64;
@@ -56,6 +65,7 @@ struct BatchArgs {
   const u64* fcur;
   u64* fnext;
   int big;                            // rows of this many entries or more belong to the slice kernels
+  int big_out;                        // ... the same for out-rows, whichever direction the kernel works in: what batch_commit_l counts
   const u64* prev;                    // heavy push levels: seen as it stood before the push kernels (else null)
   const int4* slices;                 // {vertex, first entry, end entry, big index}
   int nslices;
@@ -65,6 +75,8 @@ struct BatchArgs {
   float new_label;
   int direct_labels;                  // levels beyond the stored ones write labels as they discover
   int k;
+  unsigned int* list_len;             // batch_push_commit_kernel behind the owner kernels: the big-row list's length, reset for the next level (else null)
+  const u64* ctl;                     // a launch made ahead of the host: {qmask, pmask, kind} as the level before decided them (else null)
   float* label[64];
 };
 
@@ -79,6 +91,16 @@ struct LabelArgs {
 
 __device__ inline u64 wave_or(u64 x) { return wave_or_u64(x); }   // DPP (common.hpp): twelve LDS-crossbar permutes otherwise
 
+// the bits a pull kernel works on; false: launched ahead of a level that turned out to be none of the host loop's --
+// nothing is read or written (grid-uniform: every workgroup leaves before its first barrier)
+__device__ inline bool batch_pull_bits(const BatchArgs& a, u64& q) {
+  q = a.qmask;
+  if (!a.ctl) return true;
+  if (a.ctl[2] != (u64)kDecideHost) return false;
+  q = a.ctl[0];
+  return true;
+}
+
 struct BatchTotals {                  // per workgroup, in LDS
   u64 v[kBatchCounters];
 };
@@ -92,19 +114,24 @@ constexpr int kTransposeFrom = GRB_BATCH_TRANSPOSE_FROM;     // live sources in 
 struct WaveTotals {
   u64 nf = 0, mf = 0;
   unsigned int verts = 0;             // wave-uniform: vertices with any new bit
+  unsigned int bigs = 0;              // wave-uniform: those of them whose out-row is big (the next level's push has slices to expand)
 };
 
 // accounting (and, beyond the stored levels, labels) of a lane's new bits; wave-collective.  The 64 x 64 bit
 // matrix (lane = vertex, bit = source) is transposed with one ballot per live source, so lane s holds the
 // mask m of vertices new to source s: nf_s += popcount(m), and the degree sum comes from the degrees' bit
 // planes, mf_s += sum_b 2^b popcount(m & plane_b) -- all 64 sources in parallel, no per-source reduction.
-__device__ inline void batch_commit_l(const BatchArgs& a, WaveTotals& acc, Index v, u64 newb, bool direct, float label) {
+// (count_big = false: the light-level kernel, at 121 of the 128 VGPRs its 1024-thread workgroups may use, does not pay
+// for a count nobody reads -- after its hand-back the host launches the push helpers unconditionally)
+__device__ inline void batch_commit_l(const BatchArgs& a, WaveTotals& acc, Index v, u64 newb, bool direct, float label,
+                                      bool count_big = true) {
   const unsigned long long mv = __ballot(newb != 0);
   if (!mv) return;
   const int lane = lane_id();
   acc.verts += (unsigned int)__popcll(mv);
   unsigned int deg = 0;
   if (newb) deg = (unsigned int)(a.optr[v + 1] - a.optr[v]);
+  if (count_big) acc.bigs += (unsigned int)__popcll(__ballot(deg >= (unsigned int)a.big_out));
   u64 m = 0;
   const u64 live = wave_or(newb);
   if (__popcll(live) <= kTransposeFrom) {
@@ -152,6 +179,7 @@ __device__ inline void totals_flush_to(u64* slots, BatchTotals* lds, const WaveT
   if (acc.nf) atomicAdd(&lds->v[2 + 2 * lane], acc.nf);
   if (acc.mf) atomicAdd(&lds->v[3 + 2 * lane], acc.mf);
   if (lane == 0 && acc.verts) atomicAdd(&lds->v[0], (u64)acc.verts);
+  if (lane == 0 && acc.bigs) atomicAdd(&lds->v[kCntBigOut], (u64)acc.bigs);
   __syncthreads();
   u64* dst = slots + (size_t)(blockIdx.x & (kBatchSlots - 1)) * kBatchCounters;
   for (int i = threadIdx.x; i < kBatchCounters; i += blockDim.x)
@@ -181,10 +209,14 @@ __device__ inline u64 wave_scan_or(const Index* __restrict__ ind, const u64* __r
   return got;
 }
 
-__global__ __launch_bounds__(kBlock) void batch_seed_kernel(u64* seen, u64* w0, const Index* __restrict__ sources, int k) {
+// the sources come as kernel arguments (no host-to-device copy in front of a sweep) and are left in `sources` for the
+// light-level launch, which queues them
+struct SeedSources { Index v[64]; };
+__global__ __launch_bounds__(kBlock) void batch_seed_kernel(u64* seen, u64* w0, Index* __restrict__ sources, SeedSources src, int k) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s < k) {
-    const Index v = sources[s];
+    const Index v = src.v[s];
+    sources[s] = v;
     atomicOr(&seen[v], 1ull << s);
     atomicOr(&w0[v], 1ull << s);
   }
@@ -195,6 +227,12 @@ __global__ __launch_bounds__(kBlock) void batch_pull_kernel(BatchArgs a) {
   __shared__ Index s_pre[kWavesPerBlock][kWave];
   __shared__ Index s_p[kWavesPerBlock][kWave];
   __shared__ u64 s_acc[kWavesPerBlock][kWave];
+  u64 qmask;
+  if (!batch_pull_bits(a, qmask)) return;
+  if (qmask == 0) {                                         // every live source is pushed: the push kernels OR into all-zero words
+    for (Index v = (Index)blockIdx.x * blockDim.x + threadIdx.x; v < a.n; v += (Index)gridDim.x * blockDim.x) a.fnext[v] = 0ull;
+    return;
+  }
   totals_init(&lds);
   WaveTotals tot;
   const int lane = lane_id(), w = wave_id();
@@ -204,7 +242,7 @@ __global__ __launch_bounds__(kBlock) void batch_pull_kernel(BatchArgs a) {
     const Index v = chunk * kWave + lane;
     const bool valid = v < a.n;
     const u64 seen = valid ? a.seen[v] : ~0ull;
-    u64 need = ~seen & a.qmask;
+    u64 need = ~seen & qmask;
     Index p = 0, e = 0;
     if (need) { p = a.iptr[v]; e = a.iptr[v + 1]; }
     const bool big = e - p >= a.big;                       // probed here, finished by the slice kernels
@@ -280,9 +318,11 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
 __global__ __launch_bounds__(kBlock) void batch_pull_slices_kernel(BatchArgs a) {
   const int lane = lane_id();
   const int nwaves = gridDim.x * kWavesPerBlock;
+  u64 qmask;
+  if (!batch_pull_bits(a, qmask) || qmask == 0) return;
   for (int sl = blockIdx.x * kWavesPerBlock + wave_id(); sl < a.nslices; sl += nwaves) {
     const int4 S = a.slices[sl];
-    const u64 need = ~a.seen[S.x] & a.qmask & ~a.fnext[S.x];   // what the probes (and other slices) left open
+    const u64 need = ~a.seen[S.x] & qmask & ~a.fnext[S.x];   // what the probes (and other slices) left open
     if (!need) continue;
     const u64 got = wave_scan_or(a.iind, a.fcur, S.y, S.z, need, lane) & need;
     if (lane == 0 && got) atomicOr(&a.fnext[S.x], got);
@@ -291,20 +331,32 @@ __global__ __launch_bounds__(kBlock) void batch_pull_slices_kernel(BatchArgs a) 
 
 __global__ __launch_bounds__(kBlock) void batch_big_apply_kernel(BatchArgs a) {
   __shared__ BatchTotals lds;
+  u64 qmask;
+  if (!batch_pull_bits(a, qmask) || qmask == 0) return;
   totals_init(&lds);
   WaveTotals tot;
   const int nthreads = gridDim.x * blockDim.x;
+  // the big in-rows that still lack a bit of any of the k sources: it never rises, and once it is 0 no pull level has
+  // anything left for the slice kernels or for this one (the host stops launching them)
+  const u64 all = a.k >= 64 ? ~0ull : (1ull << a.k) - 1ull;
+  unsigned int open = 0;
   for (int base = 0; base < a.nbig; base += nthreads) {
     const int b = base + blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = b < a.nbig;
     const Index v = valid ? a.bigrows[b] : 0;
-    u64 newb = 0;
+    u64 newb = 0, left = 0;
     if (valid) {
       const u64 seen = a.seen[v];
-      newb = a.fnext[v] & ~seen & a.qmask;
+      newb = a.fnext[v] & ~seen & qmask;
       if (newb) a.seen[v] = seen | newb;
+      left = ~(seen | newb) & all;
     }
+    open += (unsigned int)__popcll(__ballot(left != 0ull));
     batch_commit(a, tot, v, newb);
+  }
+  if (lane_id() == 0) {
+    const u64 add = (u64)open + (blockIdx.x == 0 && threadIdx.x == 0 ? kInOpenCounted : 0ull);
+    if (add) atomicAdd(&lds.v[kCntInOpen], add);
   }
   totals_flush(a, &lds, tot);
 }
@@ -538,6 +590,7 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
 __global__ __launch_bounds__(kBlock) void batch_push_commit_kernel(BatchArgs a) {
   __shared__ BatchTotals lds;
   totals_init(&lds);
+  if (a.list_len && blockIdx.x == 0 && threadIdx.x == 0) *a.list_len = 0u;   // the owner kernels in front of this launch have read it
   WaveTotals tot;
   const int lane = lane_id();
   const Index nchunks = (a.n + kWave - 1) / kWave;
@@ -591,7 +644,17 @@ __global__ __launch_bounds__(kBlock) void batch_labels_kernel(LabelArgs a) {
 
 // the level's totals summed over the counter slots (left zero for the next level) and published to the host:
 // box[0 .. kBatchCounters) the totals, box[kBatchCounters] the level's sequence number, written last
-__global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64* box, u64 seq) {
+//
+// ... and the NEXT level decided here, from the totals just summed, by the rule the host uses (batch_decide.hpp): a lane
+// per source.  The decision goes to the control block behind the counters, where pull kernels launched ahead of the
+// host find it, and into the box, where the host reads it: one authority, nobody computes it a second time.
+struct DecideArgs {
+  BatchRule rule;
+  int iteration_left;                 // the level decided on may run at all
+  u64* ctl;
+};
+__global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64* box, u64 seq, DecideArgs d) {
+  __shared__ u64 s_nf[64], s_mf[64];
   const int i = threadIdx.x;
   if (i < kBatchCounters) {
     u64 t = 0;
@@ -600,6 +663,21 @@ __global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64
       counters[slot * kBatchCounters + i] = 0ull;
     }
     __hip_atomic_store(&box[i], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (i >= 2 && i < 2 + 128) ((i & 1) ? s_mf : s_nf)[(i - 2) >> 1] = t;
+  }
+  __syncthreads();
+  if (i < kWave) {
+    const u64 under = __ballot(batch_decide_under(s_nf, i, d.rule));
+    const int way = batch_decide_source(s_nf, s_mf, i, d.rule, under);
+    const u64 q = __ballot(way == 2), p = __ballot(way == 1);
+    const u64 pushed = wave_sum_u64(way == 1 ? s_mf[i] : 0ull);   // integers below 2^53: the host's sum of doubles is the same number
+    if (i == 0) {
+      const u64 kind = (u64)batch_decide_kind(q, p, (double)pushed, d.rule, d.iteration_left != 0);
+      d.ctl[0] = q; d.ctl[1] = p; d.ctl[2] = kind;
+      __hip_atomic_store(&box[kBoxDecision], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(&box[kBoxDecision + 1], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(&box[kBoxDecision + 2], kind, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
   }
   __threadfence_system();
   __syncthreads();
@@ -624,7 +702,8 @@ constexpr int kTailPiece = 256;        // edges per queue entry: one step of a w
 constexpr int kTailList = 4096;        // a workgroup's list of newly claimed vertices (beyond it a wave queues its own)
 constexpr int kTailLong = 64;          // ... of rows of more than eight pieces
 
-struct TailState {                    // zeroed by the host before every launch
+constexpr int kTailStates = 4;         // state blocks zeroed by one fill at a sweep's start: a launch takes the next clean one
+struct TailState {                    // all-zero when a launch starts
   GridBarrier bar;
   unsigned int count[4][32];          // queue lengths (one line each; [2..3]: the out-edges queued): level j reads [j & 3], appends to [(j + 1) & 3]
   u64 slots[3][kBatchSlots * kBatchCounters];
@@ -914,7 +993,7 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
         for (int r4 = 0; r4 < 4; ++r4) vq[r4] = bits[r4] && atomicOr(&Xn[dst[r4]], bits[r4]) == 0ull ? dst[r4] : -1;
         collect(qn, cn, vq, 4);
 #pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) batch_commit_l(a, tot, bits[r4] ? dst[r4] : 0, bits[r4], true, lab);
+        for (int r4 = 0; r4 < 4; ++r4) batch_commit_l(a, tot, bits[r4] ? dst[r4] : 0, bits[r4], true, lab, false);
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -1122,6 +1201,7 @@ struct SweepOwn {
   bool clean_valid = false, clean[4] = {false, false, false, false};   // the rotating arrays known all-zero, for (clean_n, clean_nstore)
   Index clean_n = 0;
   int clean_nstore = 0;
+  bool small_clean = false;                                 // the counter slots and the big-row list's length are zero, as every complete sweep leaves them
   bool warmed = false;                                      // every batch_* kernel has been launched once ...
   bool warmed_own_small = false, warmed_own_wide = false;   // ... the two owner-computes instances too (they need a matrix with ranges)
 };
@@ -1151,7 +1231,7 @@ static SweepSizes sweep_sizes(grb_matrix A) {
   z.words = (size_t)nbuf * sizeof(u64) * (size_t)n + 256;
   z.qcap = (size_t)n + (size_t)(A->nvals / kTailPiece) + 64;
   z.tail_state = (sizeof(TailState) + 255) & ~(size_t)255;
-  z.tail = z.tail_state + 3 * sizeof(u64) * z.qcap;
+  z.tail = kTailStates * z.tail_state + 3 * sizeof(u64) * z.qcap;
   z.list_ids = (sizeof(int) * (size_t)A->batch_out.nbig + 255) & ~(size_t)255;
   z.list = 256 + z.list_ids + sizeof(u64) * (size_t)A->batch_out.nbig;
   return z;
@@ -1188,7 +1268,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   } else {
     GRB_TRY(scratch(7, z.words, &p_words));
     c.bfs_prezero_ptr = nullptr;                            // slot 7 is the one-launch traversal's pre-zeroed block
-    GRB_TRY(scratch(10, sizeof(u64) * kBatchSlots * kBatchCounters, &p_cnt));
+    GRB_TRY(scratch(10, sizeof(u64) * (kBatchSlots * kBatchCounters + kBatchCtlWords), &p_cnt));
     GRB_TRY(scratch(9, sizeof(Index) * 64, &p_src));
     if (!s_ev0) {
       GRB_HIP_TRY(hipEventCreate(&s_ev0));
@@ -1240,6 +1320,10 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   a.seen = seen;
   a.counters = (u64*)p_cnt;
   a.k = k;
+  a.ctl = nullptr;
+  a.list_len = nullptr;
+  a.big_out = batch_big(false);
+  u64* const d_ctl = a.counters + kBatchSlots * kBatchCounters;   // written by every totals kernel before anybody reads it
   for (int s = 0; s < 64; ++s) a.label[s] = nullptr;
   for (int s = 0; s < k; ++s) {
     GRB_TRY(grb_vector_set_storage(v[s], GRB_DENSE));
@@ -1248,10 +1332,29 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   GRB_TRY(batch_box());
   u64 *const h_box = g_box_h, *const d_box = g_box_d;
   u64& box_seq = g_box_seq;
-  GRB_HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
+  // The counter slots are left zero by every totals kernel and the big-row list's length by the commit kernel behind the
+  // owner kernels, so a sweep that ran to its end leaves both zero; on the sweep's own buffers, which nobody else has, that
+  // is remembered, and a sweep that fails in between clears them at the next start.
+  void* p_list = own ? own->list : nullptr;
+  if (!own) GRB_TRY(scratch(11, z.list, &p_list));
+  unsigned int* const d_count = (unsigned int*)p_list;
+  if (!(own && own->small_clean)) {
+    GRB_HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
+    GRB_HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
+  }
+  if (own) own->small_clean = false;
+  // the light-level launches' state blocks, all of them now: the fill runs while the host is still enqueuing the sweep's
+  // start, not between a level's totals and the launch that waits for it
+  void* p_tail = own ? own->tail : nullptr;
+  int tail_states_used = 0;
+  if (batch_tail_limit() > 0) {
+    if (!own) GRB_TRY(scratch(8, z.tail, &p_tail));
+    GRB_HIP_TRY(hipMemsetAsync(p_tail, 0, kTailStates * z.tail_state, st));
+  }
   GRB_HIP_TRY(hipMemsetAsync(seen, 0, 2 * sizeof(u64) * (size_t)n, st));       // seen and the seeds' words
-  GRB_HIP_TRY(hipMemcpyAsync(p_src, sources, sizeof(Index) * (size_t)k, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, seen, Slot(0), (const Index*)p_src, k);
+  SeedSources seeds;
+  for (int s = 0; s < 64; ++s) seeds.v[s] = s < k ? (Index)sources[s] : 0;
+  hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, seen, Slot(0), (Index*)p_src, seeds, k);
   GRB_HIP_TRY(hipGetLastError());
 
   // per-source frontier totals of the seed level
@@ -1290,55 +1393,88 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     }
     return GRB_SUCCESS;
   };
+  // ---- direction per source: the reference's vertex-count rule (switchpoint) on that source's own frontier, and a
+  // budget on the edges pushed in one level (batch_decide.hpp): pull the sources whose own frontier passed the
+  // reference's switch point (their bits are found within a few probes, so the early exit works); push the others --
+  // unless their out-edges together exceed 0.15 of the matrix (GRB_BATCH_BUDGET: a pushed edge is a random line of seen
+  // plus an atomic on it, about 50 G edges/s on RMAT-22 against 85 G/s for a pulled entry), then the heaviest of them
+  // are pulled as well.  The host decides the sweep's first level and the one after a light-level launch; after a level
+  // of this loop the totals kernel has decided the next one on the device, and that decision is the one used.
+  BatchRule rule;
+  rule.k = k; rule.n = (long long)n; rule.nvals = (long long)A->nvals;
+  rule.mode = mode == GRB_PULLONLY ? kDecidePullOnly : mode == GRB_PUSHONLY ? kDecidePushOnly : kDecidePushPull;
+  rule.switchpoint = switchpoint; rule.budget = budget; rule.tail_limit = tail_on ? tail_edges : 0.0;
+  // Launching ahead: behind a level's totals kernel the NEXT level's pull kernels are enqueued at once, before the host
+  // has the totals -- they take their bits from the control block the totals kernel leaves, and return at once when that
+  // level is no level of this loop.  The GPU then pulls while the host turns the level round.  Stream order is all this
+  // relies on.  GRB_BATCH_AHEAD=0: wait, then launch (for A/B runs in fresh processes).
+  static const bool ahead_on = [] { const char* e = getenv("GRB_BATCH_AHEAD"); return !e || atoi(e) != 0; }();
+  const bool ahead = ahead_on && mode != GRB_PUSHONLY;
+  // where a level's words go is a PLAN until the level is known to be one of this loop: a kept slot while there are any
+  // (the label pass reads it), else a rotating array that labels as it discovers
+  struct Plan { bool keep; int fi; u64* fnext; };
+  auto plan_slot = [&](const u64* fcur) {
+    Plan p;
+    p.keep = nkept <= nstore;
+    p.fi = p.keep ? -1 : pick(fcur, nullptr, nullptr, false);
+    p.fnext = p.keep ? Slot(nkept) : pool[p.fi];
+    return p;
+  };
+  auto commit_slot = [&](const Plan& p, int it) {
+    if (p.fi >= 0) pool_clean[p.fi] = false;
+    if (p.keep) { kept_words[nkept] = p.fnext; kept_level[nkept] = it; ++nkept; } else any_direct = true;
+  };
+  bool in_done = false;                                     // every big in-row has every source's bit: nothing left for the slice kernels
+  long long big_out_new = -1;                               // big out-rows among the frontier's vertices (-1: not counted, the light-level launch's hand-back)
+  auto launch_pull = [&](BatchArgs& x) -> grb_info {
+    const BatchSlices& B = A->batch_in;
+    x.big = in_done ? INT_MAX : batch_big(true);
+    x.slices = B.d_slices; x.nslices = B.nslices; x.bigrows = B.d_rows; x.nbig = B.nbig;
+    hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, x);
+    GRB_HIP_TRY(hipGetLastError());
+    if (B.nslices > 0 && !in_done) {
+      hipLaunchKernelGGL(batch_pull_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
+                         0, st, x);
+      GRB_HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(batch_big_apply_kernel, dim3(stream_grid(B.nbig, kBlock)), dim3(kBlock), 0, st, x);
+      GRB_HIP_TRY(hipGetLastError());
+    }
+    return GRB_SUCCESS;
+  };
+  BatchDecision dec;
+  bool have_dec = false, pulled_ahead = false;
+  Plan planned = {false, -1, nullptr};
   GRB_HIP_TRY(hipEventRecord(ev0, st));
   for (; iter <= max_niter; ++iter) {
     const double t_lvl = trace ? now_us() : 0.0;
-    // ---- direction per source: the reference's vertex-count rule (switchpoint) on that source's own
-    // frontier, and a budget on the edges pushed in one level
-    u64 P = 0, Q = 0;
-    double pushed_edges = 0;
-    {
-      int order[64];
-      int m = 0;
-      for (int s = 0; s < k; ++s) if (nf_s[s] > 0) order[m++] = s;
-      if (mode == GRB_PULLONLY) { for (int i = 0; i < m; ++i) Q |= 1ull << order[i]; }
-      else if (mode == GRB_PUSHONLY) { for (int i = 0; i < m; ++i) P |= 1ull << order[i]; }
-      else {
-        // pull the sources whose own frontier passed the reference's switch point (their bits are found within
-        // a few probes, so the early exit works); push the others -- unless their out-edges together exceed 0.15
-        // of the matrix (GRB_BATCH_BUDGET: a pushed edge is a random line of seen plus an atomic on it, about
-        // 50 G edges/s on RMAT-22 against 85 G/s for a pulled entry), then the heaviest of them are pulled as well
-        std::sort(order, order + m, [&](int x, int y) { return mf_s[x] > mf_s[y]; });
-        double pushed = 0;
-        for (int i = 0; i < m; ++i)
-          if ((double)nf_s[order[i]] <= (double)switchpoint * (double)n) pushed += (double)mf_s[order[i]];
-        for (int i = 0; i < m; ++i) {
-          const int s = order[i];
-          bool pull = (double)nf_s[s] > (double)switchpoint * (double)n;
-          if (!pull && pushed > budget * (double)A->nvals) { pull = true; pushed -= (double)mf_s[s]; }
-          if (pull) Q |= 1ull << s; else P |= 1ull << s;
-        }
-      }
-    }
-    for (int s = 0; s < k; ++s) if ((P >> s) & 1ull) pushed_edges += (double)mf_s[s];
+    if (!have_dec) dec = batch_decide(nf_s, mf_s, rule, true);
+    have_dec = false;
+    if (dec.kind == kDecideDone) break;                     // no live source
+    const u64 P = dec.pmask, Q = dec.qmask;
+    const double pushed_edges = dec.pushed_edges;
     a.qmask = Q; a.pmask = P;
     a.prev = nullptr;
     a.fcur = fcur_words;
+    a.ctl = nullptr;
+    a.list_len = nullptr;
     // ---- every live source pushed and few edges to push: this level and the light ones after it in one launch
-    if (tail_on && Q == 0 && P != 0 && pushed_edges <= tail_edges) {
+    if (dec.kind == kDecideLight) {
+      pulled_ahead = false;                                 // (launched ahead, the pull kernels found this out and wrote nothing: the plan is dropped)
       int xi[3];
       xi[0] = pick(fcur_words, nullptr, nullptr, true);
       xi[1] = pick(fcur_words, pool[xi[0]], nullptr, true);
       xi[2] = pick(fcur_words, pool[xi[0]], pool[xi[1]], true);
-      void* p_tail = own ? own->tail : nullptr;
       const size_t qcap = z.qcap;
       const size_t st_bytes = z.tail_state;
-      if (!own) GRB_TRY(scratch(8, z.tail, &p_tail));
+      // the next clean state block; a fifth launch in one sweep and every later one clear the last block for themselves
+      const bool clean_state = tail_states_used < kTailStates;
+      char* const p_state = (char*)p_tail + (size_t)(clean_state ? tail_states_used : kTailStates - 1) * st_bytes;
+      ++tail_states_used;
       TailArgs t;
       t.f0 = fcur_words;
       for (int i = 0; i < 3; ++i) t.X[i] = pool[xi[i]];
-      t.st = (TailState*)p_tail;
-      for (int i = 0; i < 3; ++i) t.queue[i] = (u64*)((char*)p_tail + st_bytes) + (size_t)i * qcap;
+      t.st = (TailState*)p_state;
+      for (int i = 0; i < 3; ++i) t.queue[i] = (u64*)((char*)p_tail + kTailStates * st_bytes) + (size_t)i * qcap;
       t.box = d_box;
       t.seq = ++box_seq;
       t.iter0 = iter;
@@ -1348,7 +1484,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       t.nsrc = iter == 1 ? k : 0;
       t.per_source = per ? 1 : 0;
       a.direct_labels = 1;
-      GRB_HIP_TRY(hipMemsetAsync(p_tail, 0, st_bytes, st));
+      if (!clean_state) GRB_HIP_TRY(hipMemsetAsync(p_state, 0, st_bytes, st));
       for (int i = 0; i < 3; ++i)
         if (!pool_clean[xi[i]]) GRB_HIP_TRY(hipMemsetAsync(t.X[i], 0, sizeof(u64) * (size_t)n, st));
       hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
@@ -1373,6 +1509,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       levels += done;
       last_dir = 0;
       any_direct = true;
+      big_out_new = -1;
       for (int i = 0; i < 3; ++i) pool_clean[xi[i]] = true;
       fcur_words = t.X[(done - 1) % 3];                     // the last level run, j = done - 1, wrote X[j % 3]
       if (status != 0) pool_clean[xi[(done - 1) % 3]] = false;   // the new frontier; every other array was left all-zero
@@ -1390,29 +1527,19 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       if (status == 0) break;                               // nothing new: the traversals are over
       continue;                                             // capped (the loop condition ends it) or grown heavy again
     }
-    const bool keep = nkept <= nstore;                       // a slot left: the label pass reads this level's words
-    const int fi = keep ? -1 : pick(fcur_words, nullptr, nullptr, false);
-    a.fnext = keep ? Slot(nkept) : pool[fi];
-    if (fi >= 0) pool_clean[fi] = false;
+    const Plan slot = pulled_ahead ? planned : plan_slot(fcur_words);
+    commit_slot(slot, iter);                                // a level of this loop: the plan holds
+    a.fnext = slot.fnext;
     a.new_label = (float)(iter + 1);
-    a.direct_labels = keep ? 0 : 1;
-    if (keep) { kept_words[nkept] = a.fnext; kept_level[nkept] = iter; ++nkept; } else any_direct = true;
-    if (Q) {
-      const BatchSlices& B = A->batch_in;
-      a.big = batch_big(true);
-      a.slices = B.d_slices; a.nslices = B.nslices; a.bigrows = B.d_rows; a.nbig = B.nbig;
-      hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, a);
-      GRB_HIP_TRY(hipGetLastError());
-      if (B.nslices > 0) {
-        hipLaunchKernelGGL(batch_pull_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
-                           0, st, a);
-        GRB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(batch_big_apply_kernel, dim3(stream_grid(B.nbig, kBlock)), dim3(kBlock), 0, st, a);
-        GRB_HIP_TRY(hipGetLastError());
-      }
+    a.direct_labels = slot.keep ? 0 : 1;
+    if (pulled_ahead) {
+      // the pull kernels are already running, or done: for Q == 0 they have zeroed the words
+    } else if (Q) {
+      GRB_TRY(launch_pull(a));
     } else {
       GRB_HIP_TRY(hipMemsetAsync(a.fnext, 0, sizeof(u64) * (size_t)n, st));
     }
+    pulled_ahead = false;
     if (P) {
       const BatchSlices& B = A->batch_out;
       a.big = batch_big(false);
@@ -1424,18 +1551,16 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
         a.prev = prev;
       }
       a.slices = B.d_slices; a.nslices = B.nslices; a.bigrows = B.d_rows; a.nbig = B.nbig;
+      const bool big_rows = B.nslices > 0 && big_out_new != 0;   // none in the frontier: no slice, list or owner kernel has anything to do
       hipLaunchKernelGGL(batch_push_kernel, dim3(grid), dim3(kBlock), 0, st, a);
       GRB_HIP_TRY(hipGetLastError());
       static const bool owner_ok = [] { const char* e = getenv("GRB_BATCH_OWNER"); return !e || atoi(e) != 0; }();
-      if (B.nslices > 0 && a.prev && owner_ok && B.d_range_off) {
+      if (big_rows && a.prev && owner_ok && B.d_range_off) {
         // heavy level: the big rows' edges are settled by the owners of their destination ranges, in LDS
-        void* p_list = own ? own->list : nullptr;
         const size_t list_bytes = z.list_ids;
-        if (!own) GRB_TRY(scratch(11, z.list, &p_list));
-        unsigned int* d_count = (unsigned int*)p_list;
         int* d_list = (int*)((char*)p_list + 256);
         u64* d_list_fw = (u64*)((char*)p_list + 256 + list_bytes);
-        GRB_HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
+        a.list_len = d_count;                                // zero here; the commit kernel below puts it back to zero
         hipLaunchKernelGGL(batch_big_list_kernel, dim3(stream_grid(B.nbig, kBlock)), dim3(kBlock), 0, st, a, d_list, d_list_fw, d_count);
         GRB_HIP_TRY(hipGetLastError());
         if (B.nsmall > 0)
@@ -1452,7 +1577,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
           GRB_HIP_TRY(hipMemcpy(&hc, d_count, 4, hipMemcpyDeviceToHost));
           fprintf(stderr, "batch level %d: owner-computes push, %u of %d big rows in the frontier, %d ranges\n", iter, hc, B.nbig, B.nranges);
         }
-      } else if (B.nslices > 0) {
+      } else if (big_rows) {
         hipLaunchKernelGGL(batch_push_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
                            0, st, a);
         GRB_HIP_TRY(hipGetLastError());
@@ -1461,11 +1586,35 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       GRB_HIP_TRY(hipGetLastError());
     }
     // the totals come back through a pinned, host-coherent box the host polls: no copy, no stream wait
-    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, d_box, ++box_seq);
+    DecideArgs da;
+    da.rule = rule;
+    da.iteration_left = iter + 1 <= max_niter ? 1 : 0;
+    da.ctl = d_ctl;
+    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, d_box, ++box_seq, da);
     GRB_HIP_TRY(hipGetLastError());
+    if (ahead && iter + 1 <= max_niter) {
+      // the next level's pull kernels, behind the totals kernel that decides whether and on which bits they run
+      BatchArgs an = a;
+      an.fcur = a.fnext;
+      planned = plan_slot(an.fcur);
+      an.fnext = planned.fnext;
+      an.new_label = (float)(iter + 2);
+      an.direct_labels = planned.keep ? 0 : 1;
+      an.prev = nullptr;
+      an.qmask = 0; an.pmask = 0;
+      an.ctl = d_ctl;
+      GRB_TRY(launch_pull(an));
+      pulled_ahead = true;
+    }
     GRB_TRY(wait_box());
     u64 t[kBatchCounters];
     for (int j = 0; j < kBatchCounters; ++j) t[j] = __atomic_load_n(&h_box[j], __ATOMIC_RELAXED);
+    dec.qmask = __atomic_load_n(&h_box[kBoxDecision], __ATOMIC_RELAXED);
+    dec.pmask = __atomic_load_n(&h_box[kBoxDecision + 1], __ATOMIC_RELAXED);
+    dec.kind = (int)__atomic_load_n(&h_box[kBoxDecision + 2], __ATOMIC_RELAXED);
+    have_dec = true;
+    if ((t[kCntInOpen] & kInOpenCounted) && (t[kCntInOpen] & (kInOpenCounted - 1)) == 0) in_done = true;
+    big_out_new = (long long)t[kCntBigOut];
     ++levels;
     last_dir = Q ? 1 : 0;
     fcur_words = a.fnext;
@@ -1482,9 +1631,14 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       if (nf_s[s]) { any_left = true; last_prod[s] = iter; dir_s[s] = (int)((Q >> s) & 1ull); }
     }
     if (trace)
-      fprintf(stderr, "batch level %d: pull %d sources, push %d (%.0f edges, %s) -> vertices %llu pairs %llu  %.1f us\n",
+      fprintf(stderr, "batch level %d: pull %d sources, push %d (%.0f edges, %s) -> vertices %llu pairs %llu, big in-rows open %s%llu, "
+              "big out-rows found %lld, next level %s  %.1f us\n",
               iter, __builtin_popcountll(Q), __builtin_popcountll(P), pushed_edges, a.prev ? "claims" : "direct", t[0],
-              pairs, now_us() - t_lvl);
+              pairs, (t[kCntInOpen] & kInOpenCounted) ? "" : "(not counted) ", t[kCntInOpen] & (kInOpenCounted - 1), big_out_new,
+              dec.kind == kDecideHost ? (pulled_ahead ? "pulled ahead" : "host") : dec.kind == kDecideLight ? "light" : "none",
+              now_us() - t_lvl);
+    dec.pushed_edges = 0;
+    for (int s = 0; s < k; ++s) if ((dec.pmask >> s) & 1ull) dec.pushed_edges += (double)mf_s[s];
     if (!any_left) break;
   }
   const bool hit_cap = iter > max_niter && any_left;
@@ -1513,6 +1667,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   GRB_HIP_TRY(hipEventSynchronize(ev1));                    // the labels are in place
   GRB_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
   if (own) {
+    own->small_clean = true;
     own->clean_valid = true;
     own->clean_n = n;
     own->clean_nstore = nstore;
@@ -1553,6 +1708,7 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   a.n = 0;
   a.seen = (u64*)own->words; a.fcur = (const u64*)own->words; a.fnext = (u64*)own->words;
   a.big = batch_big(true);
+  a.big_out = batch_big(false);
   a.counters = (u64*)own->cnt;
   a.direct_labels = 1;
   GRB_HIP_TRY(hipMemsetAsync(own->cnt, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
@@ -1561,7 +1717,9 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   int* d_list = (int*)((char*)own->list + 256);
   u64* d_list_fw = (u64*)((char*)own->list + 256 + z.list_ids);
   if (!own->warmed) {
-    hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, a.seen, a.seen, (const Index*)own->src, 0);
+    SeedSources none;
+    memset(&none, 0, sizeof(none));
+    hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, a.seen, a.seen, (Index*)own->src, none, 0);
     hipLaunchKernelGGL(batch_pull_kernel, dim3(1), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(batch_pull_slices_kernel, dim3(1), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(batch_big_apply_kernel, dim3(1), dim3(kBlock), 0, st, a);
@@ -1581,7 +1739,7 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
     t.f0 = a.fcur;
     for (int i = 0; i < 3; ++i) {
       t.X[i] = a.seen;
-      t.queue[i] = (u64*)((char*)own->tail + z.tail_state) + (size_t)i * z.qcap;
+      t.queue[i] = (u64*)((char*)own->tail + kTailStates * z.tail_state) + (size_t)i * z.qcap;
     }
     t.st = (TailState*)own->tail;
     t.box = g_box_d;
@@ -1592,8 +1750,17 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
     GRB_HIP_TRY(hipMemsetAsync(own->tail, 0, z.tail_state, st));
     hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
     GRB_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, g_box_d, ++g_box_seq);
+    DecideArgs da;
+    memset(&da, 0, sizeof(da));                             // no source: the decision is "done"
+    da.ctl = a.counters + kBatchSlots * kBatchCounters;
+    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, g_box_d, ++g_box_seq, da);
     GRB_HIP_TRY(hipGetLastError());
+    a.ctl = da.ctl;                                         // ... and the pull kernels as a launch ahead of it finds them: they leave at once
+    hipLaunchKernelGGL(batch_pull_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_pull_slices_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(batch_big_apply_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    GRB_HIP_TRY(hipGetLastError());
+    a.ctl = nullptr;
   }
   // one workgroup of each owner-computes instance, once per process, on the first matrix that has such ranges
   const BatchSlices& B = A->batch_out;
@@ -1616,6 +1783,7 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   GRB_HIP_TRY(hipStreamSynchronize(st));
   if (__atomic_load_n(&g_box_h[kBatchCounters], __ATOMIC_ACQUIRE) != g_box_seq) return GRB_PANIC;
   own->warmed = true;
+  own->small_clean = true;                                  // the totals kernel left the counters zero; the list's length was set to zero above
   return GRB_SUCCESS;
 }
 
@@ -1675,13 +1843,14 @@ grb_info grb::bfs_sweep_provision(grb_matrix A) {
   if (o.words_cap < z.words || o.tail_cap < z.tail || o.list_cap < z.list) {
     if (hipStreamSynchronize(c.stream) != hipSuccess) return failed(GRB_PANIC);   // (an earlier sweep may still read the old ones)
     o.clean_valid = false;
+    o.small_clean = false;
     i = sweep_grow(&o.words, &o.words_cap, z.words);
     if (i == GRB_SUCCESS) i = sweep_grow(&o.tail, &o.tail_cap, z.tail);
     if (i == GRB_SUCCESS) i = sweep_grow(&o.list, &o.list_cap, z.list);
     if (i != GRB_SUCCESS) return failed(i);
   }
   if (!o.cnt) {
-    if (hipMalloc(&o.cnt, sizeof(u64) * kBatchSlots * kBatchCounters) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
+    if (hipMalloc(&o.cnt, sizeof(u64) * (kBatchSlots * kBatchCounters + kBatchCtlWords)) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
     if (hipMalloc(&o.src, 256) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
     if (hipMemset(o.src, 0, 256) != hipSuccess) return failed(GRB_PANIC);
   }

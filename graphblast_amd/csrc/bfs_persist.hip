@@ -1026,7 +1026,9 @@ constexpr int kCoTrain = 48;
 // Gathered traversals from which the queue runs the group as one bit-parallel sweep instead of the co-scheduled launch:
 // the smallest K of the table in docs/experiments.md R8.1 from which the sweep measured faster at that K and every larger
 // one, by more than the co-scheduled launch's run-to-run spread (RMAT-22: 0.0557 against 0.0546 at 20, 0.0488 against 0.0587 ms per
-// traversal at 24, 0.0297 against 0.0525 at 48 -- a sweep costs about 0.65 ms plus 16 us per source).
+// traversal at 24, 0.0297 against 0.0525 at 48 -- a sweep costs about 0.65 ms plus 16 us per source).  Round 9 made the sweep
+// 40-60 us shorter; at 20 it then equals the launch (R9.4: 0.0536 against 0.0545, and the driver's command built with 20 here
+// measured no gain), so the value stays.
 #ifndef GRB_BFS_SWEEP_FROM
 #define GRB_BFS_SWEEP_FROM 24
 #endif
