@@ -43,6 +43,11 @@ class BcResult(C.Structure):
                 ("loop_ms", C.c_float)]
 
 
+class CdlpResult(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("changed", C.c_int32), ("evaluated", C.c_int64), ("communities", C.c_int32),
+                ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -205,6 +210,8 @@ _SIGS = {
     "grb_ktruss": [_vp, _vp, _i, _vp, C.POINTER(TrussResult)],
     "grb_trussness": [_vp, _vp, _vp, C.POINTER(TrussResult)],
     "grb_bc": [_vp, _vp, _vp, _i, _vp, C.POINTER(BcResult)],
+    "grb_cdlp": [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(CdlpResult)],
+    "grb_cdlp_set_skip": [_i],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

@@ -751,6 +751,34 @@ def bc(v, A, sources, desc):
     return info, dict(sources=res.sources, batches=res.batches, levels=res.levels, reached=res.reached, loop_ms=res.loop_ms)
 
 
+def cdlp(v, A, desc, init=None, directed=False, max_iter=10):
+    """grb_cdlp: v = the communities of A's graph by synchronous label propagation (CDLP, as Graphalytics and LAGraph define
+    it).  A is n x n, f32 or i32; its values are never read (stored zeros are edges) and its diagonal takes no part.  N(x)
+    is a multiset: directed=False, the off-diagonal columns stored in row x of the CSR (an asymmetric A means "rows only",
+    the symmetry is not checked); directed=True, those plus the off-diagonal rows stored in column x (from the CSC), so a
+    vertex joined to x both ways counts twice.  L_0(x) = x, or init: an i32 vector of size n, either storage, all n values
+    stored, each in 0 .. n - 1.  L_t+1(x) = the smallest of the most frequent labels in { L_t(u) : u in N(x) }, L_t(x) when
+    N(x) is empty; iterations are synchronous and run until one changes nothing or max_iter have run.  v is an i32 vector
+    of size n and becomes dense; v may be init; the same inputs give the same bits.  max_iter < 1 or nvals(init) != n ->
+    GrB_INVALID_VALUE; an init value outside 0 .. n - 1 -> GrB_INVALID_INDEX; A not square or v / init not of size n ->
+    GrB_DIMENSION_MISMATCH; v or init not i32 or A outside f32 / i32 -> GrB_NOT_IMPLEMENTED; directed=True on an A without
+    its own CSC (a product result, the CSR-only format) -> GrB_INVALID_OBJECT (v unchanged on every error).  Returns (info,
+    dict(iterations = those run, the one that changed nothing included, changed = labels the last one changed, evaluated =
+    (vertex, iteration) pairs whose mode was computed: every vertex with neighbours in iteration 1, afterwards those with
+    a neighbour that changed in the iteration before, communities = distinct labels in v, loop_ms))."""
+    res = _lib.CdlpResult()
+    info = _lib.load().grb_cdlp(_h(v), _h(A), _h(init), int(directed), int(max_iter), _h(desc), C.byref(res))
+    return info, dict(iterations=res.iterations, changed=res.changed, evaluated=res.evaluated, communities=res.communities,
+                      loop_ms=res.loop_ms)
+
+
+def cdlp_set_skip(on=-1):
+    """grb_cdlp_set_skip: 1 = an iteration of cdlp evaluates only the vertices with a neighbour whose label changed in the
+    iteration before (default), 0 = every vertex with neighbours, every time (same labels; evaluated = iterations x that
+    count); < 0 queries.  Returns the previous setting."""
+    return int(_lib.load().grb_cdlp_set_skip(int(on)))
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

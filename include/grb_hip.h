@@ -910,6 +910,59 @@ typedef struct {
 } grb_bc_result;
 grb_info grb_bc(grb_vector bc, grb_matrix A, const grb_index* sources, int ns, grb_descriptor desc, grb_bc_result* result);
 
+/* Community detection by label propagation (csrc/cdlp.hip): synchronous CDLP.  The reference has no such driver
+ * (graphblas/algorithm/), so the definition is this header's own; it is Graphalytics' and LAGraph's.
+ *
+ * A is n x n, f32 or i32.  Stored values are never read: a stored zero is an edge.  Diagonal entries take no part.  N(v) is a
+ * multiset.  directed == 0: the off-diagonal column ids stored in row v of A's CSR; for a matrix with symmetric structure
+ * that is the undirected graph, the library does not check the symmetry, and an asymmetric A simply means "rows only".
+ * directed == 1: those ids plus the off-diagonal row ids stored in column v, taken from the CSC; a vertex joined to v in
+ * both directions is in N(v) twice, as in Graphalytics.
+ *
+ * L_0(v) = v when init == NULL, otherwise L_0 = init: an i32 vector of size n in either storage with all n values stored,
+ * each in 0 .. n - 1.  L_t+1(v) = the smallest label among those with the largest multiplicity in { L_t(u) : u in N(v) },
+ * and L_t+1(v) = L_t(v) when N(v) is empty.  Updates are synchronous: iteration t + 1 reads only L_t.  The call runs
+ * iterations 1, 2, ... and stops after the first one that changes no label, or after max_iter, whichever comes first
+ * (synchronous CDLP need not converge: a single edge swaps its two labels forever).
+ *
+ * grb_cdlp(labels, A, init, directed, max_iter, desc, result): labels is an i32 vector of size n; it becomes dense with all
+ * n values stored.  labels may be init.  desc may be NULL; no descriptor field is read.  result may be NULL.  The same
+ * inputs give the same bits.
+ *
+ * evaluated: a vertex is evaluated in iteration 1 when N(v) is non-empty, and in iteration t >= 2 when some u in N(v)
+ * changed its label in iteration t - 1 -- otherwise its mode cannot have changed and is not computed.  evaluated is the
+ * exact count of those (vertex, iteration) pairs.  After grb_cdlp_set_skip(0) every vertex with a non-empty N(v) is
+ * evaluated in every iteration and evaluated = iterations x that count; labels, iterations, changed and communities are
+ * identical either way.
+ *
+ * How: a label's count is kept under integer atomic adds that return the count before the add, so the largest count any
+ * add saw (the smallest label on a tie) is the mode after ONE walk over the list.  Lists of up to 8 entries take eight
+ * lanes, up to 64 a wave (no table: all pairs compared), up to 512 one wave and up to 2048 four waves with an LDS hash
+ * table, longer ones 1024 threads with one of 32 to 256 count arrays of n words in global memory (as many as fit in 128 MiB).  A vertex whose label changed marks the vertices it
+ * is a neighbour of in a bitmap (its CSC column, or both lists when directed == 1), from which the next iteration's work
+ * lists are compacted; an A without a CSC of its own has every task look at its neighbours' "changed" bits first
+ * instead.  The host reads one record per iteration (two in an iteration that ran without marks because the one before had
+ * changed every vertex, and then did not change them all).  Working memory: 36 n bytes, and 4 n bytes per list longer than 2048
+ * (for at most 256 of them and at most 128 MiB, but for 32 in any case).
+ *
+ * Every error is found before labels is written, and labels keeps what it held.  A null labels or A, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, or size(labels) != n, or size(init) != n: GRB_DIMENSION_MISMATCH; max_iter < 1,
+ * or directed outside {0, 1}, or nvals(init) != n: GRB_INVALID_VALUE; an init value outside 0 .. n - 1 (found by one
+ * reduction on the device): GRB_INVALID_INDEX; labels or init not i32, or A outside f32 / i32: GRB_NOT_IMPLEMENTED;
+ * directed == 1 and an A without a CSC of its own (a product result, the CSR-only matrix format): GRB_INVALID_OBJECT, as
+ * grb_ktruss; a failed device allocation: GRB_OUT_OF_MEMORY.  directed == 0 reads only the CSR of such a matrix, so it
+ * works on a product result and in the CSR-only matrix format.  n = 0 or an A without entries is a success: labels = L_0,
+ * iterations = 1, changed = 0. */
+typedef struct {
+  int32_t iterations;         /* iterations run, the one that changed nothing included                                 */
+  int32_t changed;            /* vertices whose label the last iteration changed (0 = a fixed point)                   */
+  int64_t evaluated;          /* (vertex, iteration) pairs whose mode was computed, see above                          */
+  int32_t communities;        /* distinct labels in the result                                                         */
+  float   loop_ms;            /* HIP-event time of the iterations                                                      */
+} grb_cdlp_result;
+grb_info grb_cdlp(grb_vector labels, grb_matrix A, grb_vector init, int directed, int max_iter, grb_descriptor desc, grb_cdlp_result* result);
+int grb_cdlp_set_skip(int on);   /* 1 (default) / 0; < 0 queries; returns the previous setting */
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
