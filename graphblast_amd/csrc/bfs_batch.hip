@@ -469,8 +469,16 @@ __global__ __launch_bounds__(kBlock) void batch_push_slices_kernel(BatchArgs a) 
 constexpr int kOwnRows = 8192;         // 64 KiB of LDS: two workgroups of 1024 per CU
 constexpr int kOwnSmallRows = 2048;
 
+// The offsets table is row-major, off[bi * S + b] = where big row bi enters range b, with the stride S = R + 1 rounded
+// up to 32 entries: a row's offsets start on a 128-byte line, and the two an owner needs for a list entry (b and b + 1)
+// are neighbours.  A heavy level has a few per cent of the big rows in its frontier, in arbitrary order (the vertex ids
+// are permuted, the list is appended to with atomics), so the range-major table this replaces gave an owner two lines
+// per list entry with one useful word each -- most of the wide instance's HBM traffic; here a list entry's line is
+// shared by the owners of the 32 neighbouring ranges, which run at the same time.
+static inline long long own_off_stride(long long R) { return (R + 1 + 31) & ~31ll; }
+
 __global__ void batch_range_off_kernel(const Index* __restrict__ optr, const Index* __restrict__ oind,
-                                       const Index* __restrict__ bigrows, int nbig, int R, const Index* __restrict__ bounds,
+                                       const Index* __restrict__ bigrows, int nbig, int R, int S, const Index* __restrict__ bounds,
                                        Index* __restrict__ off) {
   const long long total = (long long)nbig * (R + 1);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -482,7 +490,7 @@ __global__ void batch_range_off_kernel(const Index* __restrict__ optr, const Ind
       const Index mid = lo + (hi - lo) / 2;
       if ((long long)oind[mid] < key) lo = mid + 1; else hi = mid;
     }
-    off[(size_t)b * nbig + bi] = lo;                       // range-major: a range's owner reads neighbouring rows' offsets from one line
+    off[(size_t)bi * S + b] = lo;                          // b fastest: neighbouring threads store neighbouring words (the padding is never read)
   }
 }
 
@@ -513,7 +521,7 @@ __global__ __launch_bounds__(kBlock) void batch_big_list_kernel(BatchArgs a, int
 // (<= 2 Ki rows, 16 KiB of LDS, 512 threads: four workgroups per CU -- a workgroup's work is a short chain of
 // dependent steps, and with one per CU the chip mostly waits) and the wide ones (two per CU): 27 + 77 us.
 template <int kRows, int kThreads>
-__global__ __launch_bounds__(kThreads) void batch_push_owner_kernel(BatchArgs a, const Index* __restrict__ range_off, int R,
+__global__ __launch_bounds__(kThreads) void batch_push_owner_kernel(BatchArgs a, const Index* __restrict__ range_off, int S,
                                                                     const int* __restrict__ list, const u64* __restrict__ list_fw,
                                                                     const unsigned int* __restrict__ count, const Index* __restrict__ bounds,
                                                                     const int* __restrict__ ids) {
@@ -535,8 +543,8 @@ __global__ __launch_bounds__(kThreads) void batch_push_owner_kernel(BatchArgs a,
     if (i < nlist) {
       const int bi = list[i];
       fw = list_fw[i];
-      o0 = range_off[(size_t)b * a.nbig + bi];
-      o1 = range_off[(size_t)(b + 1) * a.nbig + bi];
+      o0 = range_off[(size_t)bi * S + b];                   // neighbours: one line per list entry
+      o1 = range_off[(size_t)bi * S + b + 1];
     }
     // the pieces of a wave's 64 entries laid end to end and dealt to the lanes 256 edges at a time (as batch_push_kernel
     // does with rows): a wave pays one chain of memory latencies per 256 edges whatever the piece lengths are
@@ -1147,19 +1155,27 @@ static grb_info make_slices(grb_matrix A, bool in_edges) {
         bounds.push_back(e);
       }
       const long long R = (long long)bounds.size() - 1;
-      if (R >= 2 && (long long)rows.size() * (R + 1) <= (128ll << 20)) {
+      const long long S = own_off_stride(R);                 // the table's row stride: whole 128-byte lines
+      if (R >= 2 && (long long)rows.size() * S <= (128ll << 20)) {
         GRB_HIP_TRY(hipMalloc((void**)&B.d_range_bounds, sizeof(Index) * bounds.size()));
         GRB_HIP_TRY(hipMemcpy(B.d_range_bounds, bounds.data(), sizeof(Index) * bounds.size(), hipMemcpyHostToDevice));
-        GRB_HIP_TRY(hipMalloc((void**)&B.d_range_off, sizeof(Index) * rows.size() * (size_t)(R + 1)));
+        GRB_HIP_TRY(hipMalloc((void**)&B.d_range_off, sizeof(Index) * rows.size() * (size_t)S));
         hipLaunchKernelGGL(batch_range_off_kernel, dim3(stream_grid((long long)rows.size() * (R + 1), kBlock)), dim3(kBlock), 0,
-                           ctx().stream, A->csr.ptr, A->csr.ind, B.d_rows, (int)rows.size(), (int)R, (const Index*)B.d_range_bounds,
-                           B.d_range_off);
+                           ctx().stream, A->csr.ptr, A->csr.ind, B.d_rows, (int)rows.size(), (int)R, (int)S,
+                           (const Index*)B.d_range_bounds, B.d_range_off);
         GRB_HIP_TRY(hipGetLastError());
         B.nranges = (int)R;
         std::vector<int> ids;
+        // Within an instantiation, workgroup p runs on XCD p % 8 (round-robin dispatch): the ranges are dealt so that each
+        // XCD gets a contiguous eighth of them, and the 32 ranges that share a line of the offsets table share an L2.
         for (int pass = 0; pass < 2; ++pass) {
+          std::vector<int> mine;
           for (long long b = 0; b < R; ++b)
-            if ((bounds[(size_t)b + 1] - bounds[(size_t)b] <= kOwnSmallRows) == (pass == 0)) ids.push_back((int)b);
+            if ((bounds[(size_t)b + 1] - bounds[(size_t)b] <= kOwnSmallRows) == (pass == 0)) mine.push_back((int)b);
+          const size_t m = mine.size(), q = m / 8, r = m % 8;
+          for (size_t j = 0; j <= q; ++j)
+            for (size_t x = 0; x < 8; ++x)
+              if (j < q + (x < r ? 1 : 0)) ids.push_back(mine[x * q + std::min(x, r) + j]);
           if (pass == 0) B.nsmall = (int)ids.size();
         }
         GRB_HIP_TRY(hipMalloc((void**)&B.d_range_ids, sizeof(int) * ids.size()));
@@ -1563,19 +1579,21 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
         a.list_len = d_count;                                // zero here; the commit kernel below puts it back to zero
         hipLaunchKernelGGL(batch_big_list_kernel, dim3(stream_grid(B.nbig, kBlock)), dim3(kBlock), 0, st, a, d_list, d_list_fw, d_count);
         GRB_HIP_TRY(hipGetLastError());
+        const int S = (int)own_off_stride(B.nranges);
         if (B.nsmall > 0)
           hipLaunchKernelGGL((batch_push_owner_kernel<kOwnSmallRows, 512>), dim3(B.nsmall), dim3(512), 0, st, a, (const Index*)B.d_range_off,
-                             B.nranges, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                             S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
                              (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
         if (B.nranges > B.nsmall)
           hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(B.nranges - B.nsmall), dim3(1024), 0, st, a,
-                             (const Index*)B.d_range_off, B.nranges, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                             (const Index*)B.d_range_off, S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
                              (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + B.nsmall);
         GRB_HIP_TRY(hipGetLastError());
         if (trace) {
           unsigned int hc = 0;
           GRB_HIP_TRY(hipMemcpy(&hc, d_count, 4, hipMemcpyDeviceToHost));
-          fprintf(stderr, "batch level %d: owner-computes push, %u of %d big rows in the frontier, %d ranges\n", iter, hc, B.nbig, B.nranges);
+          fprintf(stderr, "batch level %d: owner-computes push, %u of %d big rows in the frontier, %d ranges (%d narrow, %d wide)\n", iter, hc, B.nbig,
+                  B.nranges, B.nsmall, B.nranges - B.nsmall);
         }
       } else if (big_rows) {
         hipLaunchKernelGGL(batch_push_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
@@ -1766,15 +1784,16 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   const BatchSlices& B = A->batch_out;
   if (B.d_range_off && B.nranges > 0) {
     a.nbig = B.nbig;
+    const int S = (int)own_off_stride(B.nranges);
     if (B.nsmall > 0 && !own->warmed_own_small) {
       hipLaunchKernelGGL((batch_push_owner_kernel<kOwnSmallRows, 512>), dim3(1), dim3(512), 0, st, a, (const Index*)B.d_range_off,
-                         B.nranges, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                         S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
                          (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
       own->warmed_own_small = true;
     }
     if (B.nranges > B.nsmall && !own->warmed_own_wide) {
       hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(1), dim3(1024), 0, st, a,
-                         (const Index*)B.d_range_off, B.nranges, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                         (const Index*)B.d_range_off, S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
                          (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + B.nsmall);
       own->warmed_own_wide = true;
     }
@@ -1821,7 +1840,7 @@ grb_info grb::bfs_sweep_provision(grb_matrix A) {
     if (!in) {
       list_bound = 256 + ((sizeof(int) * max_rows + 255) & ~(size_t)255) + sizeof(u64) * max_rows;   // (the big-row list: SweepSizes::list)
       const size_t max_ranges = (size_t)(3 * 256 + A->nrows / kOwnSmallRows + 2);
-      grow += sizeof(Index) * std::min<size_t>(max_rows * (max_ranges + 1), (size_t)128 << 20) + 2 * sizeof(Index) * (max_ranges + 1);
+      grow += sizeof(Index) * std::min<size_t>(max_rows * (size_t)own_off_stride((long long)max_ranges), (size_t)128 << 20) + 2 * sizeof(Index) * (max_ranges + 1);
     }
   }
   {

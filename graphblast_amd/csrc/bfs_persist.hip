@@ -1027,10 +1027,13 @@ constexpr int kCoTrain = 48;
 // the smallest K of the table in docs/experiments.md R8.1 from which the sweep measured faster at that K and every larger
 // one, by more than the co-scheduled launch's run-to-run spread (RMAT-22: 0.0557 against 0.0546 at 20, 0.0488 against 0.0587 ms per
 // traversal at 24, 0.0297 against 0.0525 at 48 -- a sweep costs about 0.65 ms plus 16 us per source).  Round 9 made the sweep
-// 40-60 us shorter; at 20 it then equals the launch (R9.4: 0.0536 against 0.0545, and the driver's command built with 20 here
-// measured no gain), so the value stays.
+// 40-60 us shorter; at 20 it then equalled the launch (R9.4: 0.0536 against 0.0545, and the driver's command built with 20 here
+// measured no gain), so the value stayed.  Round 11 took another 35-40 us off the sweep's two heavy push levels (the owners'
+// offsets table row-major, the ranges dealt to the XCDs in contiguous eighths): at 20 the sweep's worst run is now below the
+// launch's best (R11.4: 0.0516 against 0.0535 ms per traversal), and five fresh processes of the driver's 20 steps each way
+// have every run with 20 here below every run with 24 -- so 20.  At 16 the launch still wins (0.0550 against 0.0600).
 #ifndef GRB_BFS_SWEEP_FROM
-#define GRB_BFS_SWEEP_FROM 24
+#define GRB_BFS_SWEEP_FROM 20
 #endif
 struct LaunchArgs {
   PersistArgs a;

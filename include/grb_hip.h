@@ -500,7 +500,7 @@ grb_info grb_bfs_fused(grb_vector v, grb_matrix A, grb_index source, grb_descrip
  * until then; any other entry point may be called meanwhile -- it is ordered behind the queued traversals on the
  * stream).  Under co-scheduling (the default) a queued traversal starts on the device when a ticket is waited for or
  * another entry point is called, not at the enqueue (see grb_bfs_set_coschedule); a gathered group of
- * 24 or more plain traversals runs as one bit-parallel sweep inside that call (see grb_bfs_set_sweep_from).  At most
+ * 20 or more plain traversals runs as one bit-parallel sweep inside that call (see grb_bfs_set_sweep_from).  At most
  * 256 tickets may be outstanding (GRB_INSUFFICIENT_SPACE).  A traversal the one-launch kernel does not serve (road-network
  * queues, GRB_SPARSE_MATRIX_FORMAT=1) runs to its end inside the enqueue call; its ticket waits like any other.
  * grb_bfs_wait returns what grb_bfs_fused would have returned (a launch that could not finish is re-run through the
