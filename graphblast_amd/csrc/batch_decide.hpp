@@ -91,4 +91,19 @@ GRB_DECIDE_HD inline BatchDecision batch_decide(const unsigned long long* nf_s, 
   return d;
 }
 
+// The sweep's first level as a plain launch (batch_first_level_kernel): source s's row is cut into pieces of `piece`
+// edges, pre[s] .. pre[s + 1] are its pieces, pre[k] is the grid's wave count.  An empty row has no piece; a vertex
+// named twice has its pieces twice.  k <= 64, pre holds k + 1 entries (the rest, up to 65, is zeroed).
+template <typename I>
+inline void first_level_pieces(const I* row_ptr, const I* sources, int k, int piece, unsigned int* pre) {
+  unsigned int at = 0;
+  for (int s = 0; s <= 64; ++s) {
+    pre[s] = at;
+    if (s < k) {
+      const long long deg = (long long)row_ptr[(long long)sources[s] + 1] - (long long)row_ptr[sources[s]];
+      at += (unsigned int)((deg + piece - 1) / piece);
+    }
+  }
+}
+
 }  // namespace grb

@@ -47,7 +47,7 @@ constexpr int kBatchCounters = 2 + 128 + 1;   // per slot: vertices, the big in-
 constexpr int kCntInOpen = 1, kCntBigOut = 2 + 128;
 constexpr int kBatchBoxPer = kBatchCounters + 8;      // the host's box: where the light-level launch leaves TailState::cum and ::last
 constexpr int kBoxDecision = kBatchCounters + 5;      // box: {qmask, pmask, kind} of the NEXT level, as batch_totals_kernel decided it
-constexpr int kBatchCtlWords = 4;                     // the device's copy of the same three, behind the counter slots
+constexpr int kBatchCtlWords = 4;                     // the device's copy of the same three, behind the counter slots; [3]: the last light-level launch's status
 // counter kCntInOpen: the big in-rows that still lack a bit of some source (fewer than 2^31: a row index is an int), with
 // bit 62 set when the level's batch_big_apply_kernel counted them at all; counter kCntBigOut: the vertices with a new bit
 // whose out-row is big
@@ -84,6 +84,7 @@ struct LabelArgs {
   Index n;
   int k, nstored;
   const u64* seen;
+  const u64* go;                      // launched ahead of the host, behind a light-level launch: that launch's status (else null)
   const u64* W[kBatchStoreMax + 1];   // the stored levels' words ...
   float lab[kBatchStoreMax + 1];      // ... and the depth each of them assigns (0: the level the iteration cap cuts off)
   float* label[64];
@@ -209,17 +210,61 @@ __device__ inline u64 wave_scan_or(const Index* __restrict__ ind, const u64* __r
   return got;
 }
 
-// the sources come as kernel arguments (no host-to-device copy in front of a sweep) and are left in `sources` for the
-// light-level launch, which queues them
+// the sources come as kernel arguments (no host-to-device copy in front of a sweep).  w0 != nullptr: the seeds are a
+// stored level of their own; else a source's own label is written here and no word array holds the seeds (the label
+// pass leaves a pair that is seen but in no stored level alone)
 struct SeedSources { Index v[64]; };
-__global__ __launch_bounds__(kBlock) void batch_seed_kernel(u64* seen, u64* w0, Index* __restrict__ sources, SeedSources src, int k) {
+struct SeedLabels { float* p[64]; };
+__global__ __launch_bounds__(kBlock) void batch_seed_kernel(u64* seen, u64* w0, SeedSources src, SeedLabels label, int k) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s < k) {
     const Index v = src.v[s];
-    sources[s] = v;
     atomicOr(&seen[v], 1ull << s);
-    atomicOr(&w0[v], 1ull << s);
+    if (w0) atomicOr(&w0[v], 1ull << s);
+    else label.p[s][v] = 1.0f;
   }
+}
+
+// ---- the sweep's first level when every source is pushed ----------------------------------------------------------
+// The frontier is the k sources, whose rows the host knows: no queue, no scan, no co-resident grid.  A row is cut into
+// pieces of kFirstPiece edges, source s owning pieces pre[s] .. pre[s + 1] (the prefix sums come by value), a wave per
+// piece: consecutive pieces on consecutive workgroups, so a hub's row spreads over every XCD.  A discovery is one
+// returning atomicOr on seen; the claimed bit goes into the level's words (all-zero before the launch) and is counted
+// as in every host-level kernel.  A vertex named twice is two sources with the same row.
+constexpr int kFirstPiece = 4 * kWave;
+struct FirstPieces { unsigned int pre[65]; };
+static_assert(kFirstPiece == 256, "a wave takes a piece's edges four per lane");
+__global__ __launch_bounds__(kBlock) void batch_first_level_kernel(BatchArgs a, SeedSources src, FirstPieces fp) {
+  __shared__ BatchTotals lds;
+  totals_init(&lds);
+  WaveTotals tot;
+  const int lane = lane_id();
+  const unsigned int piece = blockIdx.x * kWavesPerBlock + wave_id();
+  if (piece < fp.pre[a.k]) {                                // wave-uniform
+    int s = 0;                                              // the last source whose first piece is <= piece
+#pragma unroll
+    for (int step = 32; step > 0; step >>= 1)
+      if (s + step < a.k && fp.pre[s + step] <= piece) s += step;
+    const Index u = src.v[s];
+    const u64 bit = 1ull << s;
+    const Index p = a.optr[u] + (Index)(piece - fp.pre[s]) * kFirstPiece, re = a.optr[u + 1];
+    const Index e = re - p > kFirstPiece ? p + kFirstPiece : re;
+    Index dst[4];
+    u64 nb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const Index at = p + j * kWave + lane;
+      dst[j] = at < e ? a.oind[at] : -1;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) nb[j] = dst[j] >= 0 ? (bit & ~atomicOr(&a.seen[dst[j]], bit)) : 0ull;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (nb[j]) atomicOr(&a.fnext[dst[j]], nb[j]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) batch_commit_l(a, tot, nb[j] ? dst[j] : 0, nb[j], a.direct_labels != 0, a.new_label);
+  }
+  totals_flush(a, &lds, tot);
 }
 
 __global__ __launch_bounds__(kBlock) void batch_pull_kernel(BatchArgs a) {
@@ -623,6 +668,7 @@ __global__ __launch_bounds__(kBlock) void batch_push_commit_kernel(BatchArgs a) 
 // the depth vectors from the stored level words: full 256-byte stores, every element written once
 __global__ __launch_bounds__(kBlock) void batch_labels_kernel(LabelArgs a) {
   __shared__ float s_lab[32];
+  if (a.go && *a.go == 2ull) return;                        // the launch handed a level back: the sweep goes on, nothing is read or written (grid-uniform)
   if (threadIdx.x < 32) s_lab[threadIdx.x] = threadIdx.x >= 1 && (int)threadIdx.x <= a.nstored ? a.lab[threadIdx.x - 1] : 0.f;
   __syncthreads();
   const int lane = lane_id();
@@ -694,8 +740,9 @@ __global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64
 
 // ---- the light levels in one launch ----------------------------------------------------------------------------------
 // A level that pushes a few thousand edges costs what its launches cost: four kernels over all n words, a totals
-// kernel and a host round trip -- 45-100 us for microseconds of work, on the first level of a sweep and on every level
-// of its tail (and on EVERY level of a high-diameter graph, where 64 small frontiers never grow).  While every live
+// kernel and a host round trip -- 45-100 us for microseconds of work, on every level of a sweep's tail (and on EVERY
+// level of a high-diameter graph, where 64 small frontiers never grow; a sweep's first level, whose frontier the host
+// knows, is batch_first_level_kernel's, and a launch that follows it starts from that level's kept words).  While every live
 // source is pushed and the level's out-edges stay under a limit, the levels run inside one co-resident launch
 // instead: the frontier is a QUEUE of {vertex, first edge} pieces (rows cut at kTailPiece edges, so a hub that turns
 // up is shared by many waves), a wave lays the edges of 64 pieces end to end and deals them to its lanes, a claimed
@@ -727,11 +774,10 @@ struct TailArgs {
   u64* queue[3];                      // entries (first edge << 32 | vertex), vertex complemented on all but a row's first piece
   TailState* st;
   u64* box;                           // host-coherent: the last level's totals, then {seq, levels, edges, pairs, status}
+  u64* status;                        // the device's copy of the status, for a label pass enqueued behind this launch
   u64 seq;
   int iter0, max_niter;
   unsigned long long edge_limit;      // leave when the next level would push more out-edges than this
-  const Index* src;                   // the sweep's first level: the sources (nsrc > 0), else the words of f0 are scanned
-  int nsrc;
   int per_source;                     // the caller wants every source's own totals (the queue's sweep): box[kBatchBoxPer ..]
 };
 
@@ -891,19 +937,7 @@ ince = (unsigned int)wave_incl_scan_u32((unsigned)ince);
   if (threadIdx.x == 0) s_nlist = 0;
   __syncthreads();
 
-  if (t.nsrc > 0) {                                         // the first queue of a sweep's first level: the sources themselves
-    if (gw == 0) {
-      const Index u = lane < t.nsrc ? t.src[lane] : -1;
-      // a vertex named twice is queued once: by the lane of its lowest source
-      bool first = u >= 0;
-      for (int o = 0; o < kWave; ++o) {
-        const Index other = __shfl(u, o, kWave);
-        if (o < lane && other == u) first = false;
-      }
-      const Index vq[4] = {first ? u : -1, -1, -1, -1};
-      collect(t.queue[0], &st->count[0][0], vq, 1);
-    }
-  } else {                                                  // otherwise one pass over the stored frontier words, four chunks in flight
+  {                                                         // the first queue: one pass over the stored frontier words, four chunks in flight
     const Index nchunks = (a.n + kWave - 1) / kWave;
     for (Index chunk = (Index)gw * 4; chunk < nchunks; chunk += (Index)nw * 4) {
       u64 fw[4];
@@ -1068,6 +1102,7 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
       __hip_atomic_store(&t.box[kBatchCounters + 2], (u64)cum_edges, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&t.box[kBatchCounters + 3], (u64)cum_pairs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&t.box[kBatchCounters + 4], (u64)status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      *t.status = (u64)status;
     }
     if (t.per_source)
       for (int i = threadIdx.x; i < 128 + 64; i += kPThreads)
@@ -1211,7 +1246,7 @@ extern "C" long long grb_bfs_batch_set_tail(long long edges) { GRB_API_ENTER_NOI
 // sweep must not find it taken.
 namespace {
 struct SweepOwn {
-  void *words = nullptr, *cnt = nullptr, *src = nullptr, *tail = nullptr, *list = nullptr;
+  void *words = nullptr, *cnt = nullptr, *tail = nullptr, *list = nullptr;
   size_t words_cap = 0, tail_cap = 0, list_cap = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool clean_valid = false, clean[4] = {false, false, false, false};   // the rotating arrays known all-zero, for (clean_n, clean_nstore)
@@ -1274,18 +1309,17 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   const Index n = A->nrows;
   const SweepSizes z = sweep_sizes(A);
   const int nstore = z.nstore;
-  void *p_words, *p_cnt, *p_src;
+  void *p_words, *p_cnt;
   static hipEvent_t s_ev0 = nullptr, s_ev1 = nullptr;
   hipEvent_t ev0, ev1;
   if (own) {
     if (!own->words || own->words_cap < z.words || own->tail_cap < z.tail || own->list_cap < z.list || !own->ev0) return GRB_OUT_OF_MEMORY;
-    p_words = own->words; p_cnt = own->cnt; p_src = own->src;
+    p_words = own->words; p_cnt = own->cnt;
     ev0 = own->ev0; ev1 = own->ev1;
   } else {
     GRB_TRY(scratch(7, z.words, &p_words));
     c.bfs_prezero_ptr = nullptr;                            // slot 7 is the one-launch traversal's pre-zeroed block
     GRB_TRY(scratch(10, sizeof(u64) * (kBatchSlots * kBatchCounters + kBatchCtlWords), &p_cnt));
-    GRB_TRY(scratch(9, sizeof(Index) * 64, &p_src));
     if (!s_ev0) {
       GRB_HIP_TRY(hipEventCreate(&s_ev0));
       GRB_HIP_TRY(hipEventCreate(&s_ev1));
@@ -1293,7 +1327,8 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     ev0 = s_ev0; ev1 = s_ev1;
   }
   u64* seen = (u64*)p_words;
-  // level words: slot 0 .. nstore are kept for the label pass (which level each holds is recorded as it is taken);
+  // level words: slot 0 .. nstore are kept for the label pass (which level each holds is recorded as it is taken; slot 0
+  // the seeds, or level 1 when the first level is the plain launch);
   // four more rotate -- a level beyond the kept ones (it labels as it discovers), the copy of `seen` a heavy push
   // compares against, the three word arrays of the light-level launch
   auto Slot = [&](int i) -> u64* { return seen + (size_t)(1 + i) * (size_t)n; };
@@ -1324,7 +1359,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   };
   const u64* kept_words[kBatchStoreMax + 1];
   int kept_level[kBatchStoreMax + 1];
-  int nkept = 1;                                            // the seeds
+  int nkept = 1;                                            // the seeds (taken back below when the first level needs no seed words)
   kept_words[0] = Slot(0);
   kept_level[0] = 0;
   bool any_direct = false;
@@ -1370,8 +1405,6 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   GRB_HIP_TRY(hipMemsetAsync(seen, 0, 2 * sizeof(u64) * (size_t)n, st));       // seen and the seeds' words
   SeedSources seeds;
   for (int s = 0; s < 64; ++s) seeds.v[s] = s < k ? (Index)sources[s] : 0;
-  hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, seen, Slot(0), (Index*)p_src, seeds, k);
-  GRB_HIP_TRY(hipGetLastError());
 
   // per-source frontier totals of the seed level
   unsigned long long nf_s[64], mf_s[64];
@@ -1457,9 +1490,49 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     }
     return GRB_SUCCESS;
   };
+  // the depth vectors from the kept levels as they stand; go != nullptr: only if that status word says the sweep is over
+  bool labels_done = false;
+  auto launch_labels = [&](const u64* go) -> grb_info {
+    LabelArgs L;
+    L.n = n; L.k = k;
+    L.nstored = nkept;
+    L.seen = seen;
+    L.go = go;
+    for (int i = 0; i <= kBatchStoreMax; ++i) {
+      L.W[i] = i < nkept ? kept_words[i] : nullptr;
+      // discovered by the last allowed iteration: never assigned (bfs.hpp:48-66)
+      L.lab[i] = i < nkept && kept_level[i] + 1 <= max_niter ? (float)(kept_level[i] + 1) : 0.f;
+    }
+    for (int s = 0; s < 64; ++s) L.label[s] = a.label[s];
+    hipLaunchKernelGGL(batch_labels_kernel, dim3(grid), dim3(kBlock), 0, st, L);
+    GRB_HIP_TRY(hipGetLastError());
+    return GRB_SUCCESS;
+  };
   BatchDecision dec;
   bool have_dec = false, pulled_ahead = false;
   Plan planned = {false, -1, nullptr};
+  // The first level: when the rule pushes every source (light or not), it runs as a host level whose push is
+  // batch_first_level_kernel.  The seeds then need no words of their own -- their labels are written by the seed kernel,
+  // directly -- and Slot(0) takes the level's words.  Any source pulled (pull-only rules, a switch point at 0, sources over
+  // the budget): the seeds are a stored level and the level runs through the general kernels.
+  bool first_plain = false;
+  if (max_niter >= 1) {
+    dec = batch_decide(nf_s, mf_s, rule, true);
+    have_dec = true;
+    first_plain = dec.kind != kDecideDone && dec.qmask == 0;
+  }
+  {
+    SeedLabels seed_labels;
+    for (int s = 0; s < 64; ++s) seed_labels.p[s] = a.label[s];
+    hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, seen, first_plain ? (u64*)nullptr : Slot(0), seeds, seed_labels, k);
+    GRB_HIP_TRY(hipGetLastError());
+  }
+  if (first_plain) {
+    dec.kind = kDecideHost;
+    nkept = 0;                                              // no seed words: plan_slot gives Slot(0) to level 1
+    fcur_words = nullptr;
+    any_direct = true;                                      // the sources' own labels
+  }
   GRB_HIP_TRY(hipEventRecord(ev0, st));
   for (; iter <= max_niter; ++iter) {
     const double t_lvl = trace ? now_us() : 0.0;
@@ -1492,12 +1565,11 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       t.st = (TailState*)p_state;
       for (int i = 0; i < 3; ++i) t.queue[i] = (u64*)((char*)p_tail + kTailStates * st_bytes) + (size_t)i * qcap;
       t.box = d_box;
+      t.status = d_ctl + 3;
       t.seq = ++box_seq;
       t.iter0 = iter;
       t.max_niter = max_niter;
       t.edge_limit = (unsigned long long)tail_edges;
-      t.src = (const Index*)p_src;
-      t.nsrc = iter == 1 ? k : 0;
       t.per_source = per ? 1 : 0;
       a.direct_labels = 1;
       if (!clean_state) GRB_HIP_TRY(hipMemsetAsync(p_state, 0, st_bytes, st));
@@ -1505,9 +1577,13 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
         if (!pool_clean[xi[i]]) GRB_HIP_TRY(hipMemsetAsync(t.X[i], 0, sizeof(u64) * (size_t)n, st));
       hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
       GRB_HIP_TRY(hipGetLastError());
+      // the label pass behind it, before the host has the box: it reads the launch's status from the control block and
+      // leaves at once when the sweep goes on.  A light-level launch adds no kept level, so its arguments are known.
+      if (ahead) GRB_TRY(launch_labels(d_ctl + 3));
       GRB_TRY(wait_box());                                   // any number of levels; GRB_PANIC: a grid barrier gave up
       const int done = (int)h_box[kBatchCounters + 1];
       const int status = (int)h_box[kBatchCounters + 4];
+      labels_done = ahead && status != 2;
       edges += h_box[kBatchCounters + 2];
       reached += h_box[kBatchCounters + 3];
       any_left = false;
@@ -1548,7 +1624,15 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     a.fnext = slot.fnext;
     a.new_label = (float)(iter + 1);
     a.direct_labels = slot.keep ? 0 : 1;
-    if (pulled_ahead) {
+    const bool plain_level = first_plain && iter == 1;
+    if (plain_level) {
+      // the sources' rows, a wave per piece, into Slot(0): the fill at the sweep's start has zeroed it
+      FirstPieces fp;
+      first_level_pieces(A->h_csr_ptr.data(), seeds.v, k, kFirstPiece, fp.pre);
+      hipLaunchKernelGGL(batch_first_level_kernel, dim3(fp.pre[k] > 0 ? (fp.pre[k] + kWavesPerBlock - 1) / kWavesPerBlock : 1u), dim3(kBlock),
+                         0, st, a, seeds, fp);
+      GRB_HIP_TRY(hipGetLastError());
+    } else if (pulled_ahead) {
       // the pull kernels are already running, or done: for Q == 0 they have zeroed the words
     } else if (Q) {
       GRB_TRY(launch_pull(a));
@@ -1556,7 +1640,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       GRB_HIP_TRY(hipMemsetAsync(a.fnext, 0, sizeof(u64) * (size_t)n, st));
     }
     pulled_ahead = false;
-    if (P) {
+    if (P && !plain_level) {
       const BatchSlices& B = A->batch_out;
       a.big = batch_big(false);
       if (pushed_edges > 0.5 * (double)n) {                 // heavy: claims only, the new bits read back against a copy
@@ -1660,21 +1744,8 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     if (!any_left) break;
   }
   const bool hit_cap = iter > max_niter && any_left;
-  // ---- the depth vectors
-  {
-    LabelArgs L;
-    L.n = n; L.k = k;
-    L.nstored = nkept;
-    L.seen = seen;
-    for (int i = 0; i <= kBatchStoreMax; ++i) {
-      L.W[i] = i < nkept ? kept_words[i] : nullptr;
-      // discovered by the last allowed iteration: never assigned (bfs.hpp:48-66)
-      L.lab[i] = i < nkept && kept_level[i] + 1 <= max_niter ? (float)(kept_level[i] + 1) : 0.f;
-    }
-    for (int s = 0; s < 64; ++s) L.label[s] = a.label[s];
-    hipLaunchKernelGGL(batch_labels_kernel, dim3(grid), dim3(kBlock), 0, st, L);
-    GRB_HIP_TRY(hipGetLastError());
-  }
+  // ---- the depth vectors (unless the pass enqueued behind the closing light-level launch has written them)
+  if (!labels_done) GRB_TRY(launch_labels(nullptr));
   if (hit_cap && any_direct) {
     // vertices discovered by the last allowed iteration are never assigned by the reference loop (bfs.hpp:48-66)
     hipLaunchKernelGGL(batch_unlabel_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, a,
@@ -1737,7 +1808,12 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   if (!own->warmed) {
     SeedSources none;
     memset(&none, 0, sizeof(none));
-    hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, a.seen, a.seen, (Index*)own->src, none, 0);
+    SeedLabels no_labels;
+    memset(&no_labels, 0, sizeof(no_labels));
+    FirstPieces no_pieces;
+    memset(&no_pieces, 0, sizeof(no_pieces));
+    hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, a.seen, a.seen, none, no_labels, 0);
+    hipLaunchKernelGGL(batch_first_level_kernel, dim3(1), dim3(kBlock), 0, st, a, none, no_pieces);   // k = 0: no piece
     hipLaunchKernelGGL(batch_pull_kernel, dim3(1), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(batch_pull_slices_kernel, dim3(1), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(batch_big_apply_kernel, dim3(1), dim3(kBlock), 0, st, a);
@@ -1761,9 +1837,9 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
     }
     t.st = (TailState*)own->tail;
     t.box = g_box_d;
+    t.status = a.counters + kBatchSlots * kBatchCounters + 3;
     t.seq = ++g_box_seq;
     t.iter0 = 1; t.max_niter = 1;
-    t.src = (const Index*)own->src;
     t.per_source = 1;
     GRB_HIP_TRY(hipMemsetAsync(own->tail, 0, z.tail_state, st));
     hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
@@ -1870,8 +1946,6 @@ grb_info grb::bfs_sweep_provision(grb_matrix A) {
   }
   if (!o.cnt) {
     if (hipMalloc(&o.cnt, sizeof(u64) * (kBatchSlots * kBatchCounters + kBatchCtlWords)) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
-    if (hipMalloc(&o.src, 256) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
-    if (hipMemset(o.src, 0, 256) != hipSuccess) return failed(GRB_PANIC);
   }
   if (!o.ev0) {
     if (hipEventCreate(&o.ev0) != hipSuccess || hipEventCreate(&o.ev1) != hipSuccess) return failed(GRB_PANIC);

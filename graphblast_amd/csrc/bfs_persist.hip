@@ -1031,7 +1031,10 @@ constexpr int kCoTrain = 48;
 // measured no gain), so the value stayed.  Round 11 took another 35-40 us off the sweep's two heavy push levels (the owners'
 // offsets table row-major, the ranges dealt to the XCDs in contiguous eighths): at 20 the sweep's worst run is now below the
 // launch's best (R11.4: 0.0516 against 0.0535 ms per traversal), and five fresh processes of the driver's 20 steps each way
-// have every run with 20 here below every run with 24 -- so 20.  At 16 the launch still wins (0.0550 against 0.0600).
+// have every run with 20 here below every run with 24 -- so 20.  At 16 the launch still won (0.0550 against 0.0600).  Round 12
+// made the sweep 130-140 us shorter (its first level a plain launch, the label pass ahead): at 16 the two now tie (R12.4: sweep
+// 0.0541-0.0542, worst 0.0549-0.0551, against the launch's best 0.0546-0.0548 -- the rule is not met), and the driver's 16 steps
+// built with 16 here measured 0.9 % SLOWER than with 20.  It stays 20.
 #ifndef GRB_BFS_SWEEP_FROM
 #define GRB_BFS_SWEEP_FROM 20
 #endif
