@@ -70,15 +70,18 @@ __device__ __forceinline__ void cd_mark(unsigned int* __restrict__ bits, Index w
 }
 
 // f(u) for every entry u of ind[b, e), thread t of nt: 16 bytes a lane where a whole aligned quad lies inside, eight
-// entries per lane and step; g(u) turns an entry into what f takes (a gather: all eight are in flight before the first f)
+// entries per lane and step; g(u) turns an entry into what f takes (a gather: all eight are in flight before the first f).
+// ind may be an adopted array that starts at any 4-byte boundary: then every quad goes entry by entry (the same for the
+// whole launch, so no wave diverges on it)
 template <typename G, typename F>
 __device__ __forceinline__ void cd_stream(const Index* __restrict__ ind, Index b, Index e, int t, int nt, G g, F f) {
+  const bool wide = (reinterpret_cast<uintptr_t>(ind) & 15u) == 0;
   for (Index x0 = (b & ~3) + 4 * t; x0 < e; x0 += 8 * nt) {
     Index u[8];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const Index x = x0 + h * 4 * nt;
-      if (x >= b && x + 4 <= e) {
+      if (wide && x >= b && x + 4 <= e) {
         const int4 q = *reinterpret_cast<const int4*>(ind + x);
         u[4 * h] = q.x; u[4 * h + 1] = q.y; u[4 * h + 2] = q.z; u[4 * h + 3] = q.w;
       } else {

@@ -152,7 +152,11 @@ grb_info grb_vector_build_sparse(grb_vector v, const grb_index* indices, const v
 /* build(values, nvals) -> dense; host array. */
 grb_info grb_vector_build_dense(grb_vector v, const void* values, grb_index nvals);
 /* build(T* values, nvals) / build(Index*, T*, nvals): adopt caller DEVICE pointers
- * without ownership (dense_vector.hpp:215-224, sparse_vector.hpp:164-175). */
+ * without ownership (dense_vector.hpp:215-224, sparse_vector.hpp:164-175).
+ * Adopted pointers (here, in grb_matrix_adopt_device_csr, and the raw pointers of grb_k_spmv / grb_spmm) need 4-byte
+ * alignment only: where a kernel has a 16-byte path it looks at the pointer and falls back to 4-byte accesses, and the
+ * library never writes outside [ptr, ptr + nvals).  An adopted sparse vector that is used as an OUTPUT must have room
+ * for nsize entries in both arrays (the library cannot check that); as an input nvals entries suffice. */
 grb_info grb_vector_adopt_dense(grb_vector v, void* d_values, grb_index nvals);
 grb_info grb_vector_adopt_sparse(grb_vector v, grb_index* d_indices, void* d_values,
                                  grb_index nvals);
@@ -196,7 +200,8 @@ grb_info grb_matrix_build_csr(grb_matrix A, const grb_index* csr_row_ptr, const 
                               const void* csr_val, grb_index nvals, const grb_index* csc_col_ptr,
                               const grb_index* csc_row_ind, const void* csc_val);
 /* build(row_ptr, col_ind, values, nvals) adopting DEVICE CSR (+ optional CSC) pointers
- * without ownership (sparse_matrix.hpp:417-435). */
+ * without ownership (sparse_matrix.hpp:417-435).  Every array may start at any 4-byte boundary (see
+ * grb_vector_adopt_dense); the library only reads them. */
 grb_info grb_matrix_adopt_device_csr(grb_matrix A, grb_index* d_csr_row_ptr, grb_index* d_csr_col_ind,
                                      void* d_csr_val, grb_index nvals, grb_index* d_csc_col_ptr,
                                      grb_index* d_csc_row_ind, void* d_csc_val);

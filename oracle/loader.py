@@ -134,7 +134,7 @@ def coo2csc(rows, cols, vals, nrows, ncols):
 
 def csr2csc(ptr, ind, val, nrows, ncols):
     rows = np.repeat(np.arange(nrows, dtype=Index), np.diff(ptr))
-    return coo2csc(rows, ind, val, ncols, nrows)
+    return coo2csc(rows, ind, val, nrows, ncols)
 
 
 def cache_name(fname, is_undirected=True, remove_self_loops=True):
