@@ -48,6 +48,11 @@ class CdlpResult(C.Structure):
                 ("loop_ms", C.c_float)]
 
 
+class LccResult(C.Structure):
+    _fields_ = [("edges", C.c_int64), ("triangles", C.c_int64), ("closed", C.c_int64), ("wedges", C.c_int64),
+                ("max_degree", C.c_int32), ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -212,6 +217,7 @@ _SIGS = {
     "grb_bc": [_vp, _vp, _vp, _i, _vp, C.POINTER(BcResult)],
     "grb_cdlp": [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(CdlpResult)],
     "grb_cdlp_set_skip": [_i],
+    "grb_lcc": [_vp, _vp, _i, _vp, C.POINTER(LccResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

@@ -779,6 +779,26 @@ def cdlp_set_skip(on=-1):
     return int(_lib.load().grb_cdlp_set_skip(int(on)))
 
 
+def lcc(v, A, desc, directed=False):
+    """grb_lcc: v = the local clustering coefficient of every vertex of A's graph (LCC, as Graphalytics and LAGraph define
+    it).  A is n x n, f32 or i32; its values are never read (stored zeros are edges) and its diagonal takes no part.  With
+    E = the stored off-diagonal entries, N(x) = { u != x : (x, u) in E or (u, x) in E } is a SET (a vertex joined both ways
+    is in it once; cdlp's N(x) is a multiset), d(x) = |N(x)|, num(x) = the number of stored entries (u, w), u != w, with both
+    ends in N(x) -- directed entries -- and v[x] = num(x) / (d(x) (d(x) - 1)) when d(x) >= 2, else exactly 0; on a
+    symmetric structure that is 2 tri(x) / (d (d - 1)).  directed=False: A's structure is symmetric and only the CSR is
+    read; with a CSC of its own an asymmetric A -> GrB_INVALID_VALUE, without one (a product result, the CSR-only format)
+    the caller vouches for it.  directed=True: any structure, CSR and CSC are read; an A without its own CSC ->
+    GrB_INVALID_OBJECT.  v is an f32 vector of size n and becomes dense; num and d are exact integers, the quotient is f64
+    rounded to f32 once; the same inputs give the same bits.  A not square or v not of size n -> GrB_DIMENSION_MISMATCH;
+    v not f32 or A outside f32 / i32 -> GrB_NOT_IMPLEMENTED (v unchanged on every error).  Returns (info, dict(edges =
+    unordered joined pairs, triangles of that undirected graph, closed = the sum of num, wedges = the sum of d (d - 1),
+    max_degree, loop_ms))."""
+    res = _lib.LccResult()
+    info = _lib.load().grb_lcc(_h(v), _h(A), int(directed), _h(desc), C.byref(res))
+    return info, dict(edges=res.edges, triangles=res.triangles, closed=res.closed, wedges=res.wedges,
+                      max_degree=res.max_degree, loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

@@ -968,6 +968,63 @@ typedef struct {
 grb_info grb_cdlp(grb_vector labels, grb_matrix A, grb_vector init, int directed, int max_iter, grb_descriptor desc, grb_cdlp_result* result);
 int grb_cdlp_set_skip(int on);   /* 1 (default) / 0; < 0 queries; returns the previous setting */
 
+/* The local clustering coefficient (csrc/lcc.hip).  The reference has no such driver (graphblas/algorithm/), so the
+ * definition is this header's own; it is Graphalytics' and LAGraph's.
+ *
+ * A is n x n, f32 or i32.  Stored values are never read: a stored zero is an edge.  Diagonal entries take no part.
+ *   E      = { (i, j) : A(i, j) stored, i != j }
+ *   N(v)   = { u != v : (v, u) in E or (u, v) in E }, a SET: a vertex joined to v both ways is in it once (grb_cdlp's N(v)
+ *            is a multiset and counts such a vertex twice; this one does not)
+ *   d(v)   = |N(v)|
+ *   num(v) = |{ (u, w) : u, w in N(v), u != w, (u, w) in E }|, the number of DIRECTED stored entries between neighbours of v
+ *   lcc(v) = num(v) / (d(v) (d(v) - 1)) when d(v) >= 2, else exactly 0.
+ * On a matrix with symmetric structure this is the usual 2 tri(v) / (d (d - 1)).  One formula serves both cases; directed
+ * only says what the library may read and assume:
+ *   directed == 0   A's structure is symmetric and only the CSR is read.  When A has a CSC of its own the symmetry is
+ *                   checked by one comparison on the device, and an asymmetric A is GRB_INVALID_VALUE.  The verdict is
+ *                   part of the call's one host read, so the whole computation has run by then: on an asymmetric A the
+ *                   lists are not bounded by sqrt(2 entries) and the error may take far longer than a good call.  An A without a CSC
+ *                   of its own (a product result, the CSR-only matrix format) is taken on the caller's word: nothing is
+ *                   read or written out of bounds whatever its structure is, and the values are then unspecified.
+ *   directed == 1   any structure; the CSR and the CSC are both read.  An A without a CSC of its own is
+ *                   GRB_INVALID_OBJECT, as in grb_cdlp.
+ *
+ * grb_lcc(lcc, A, directed, desc, result): lcc is an f32 vector of size n; it becomes dense with all n values stored.  desc
+ * may be NULL; no descriptor field is read.  result may be NULL.
+ *
+ * Arithmetic: num(v) and d(v) are exact integers, num in 64 bits (d (d - 1) exceeds 2^32 on a hub).  The value is the f64
+ * quotient (double)num / ((double)d * (double)(d - 1)) rounded to f32 once; both operands are below 2^53, so the quotient
+ * is the correctly rounded one.  The same inputs give the same bits, every time.
+ *
+ * How: with m(v, u) in {1, 2} = how many of (v, u) and (u, v) are stored, num(a) = the sum of m(b, c) over the triangles
+ * {a, b, c} of the undirected graph.  The call builds that graph on the device, structure only: row v = N(v) ascending (CSR
+ * row v merged with CSC column v when directed == 1), every entry with the bit m - 1 on top of its 32-bit index.  Every
+ * vertex keeps the neighbours that rank above it by (d, id) -- no list is longer than sqrt(2 entries) -- and every
+ * triangle is enumerated ONCE: per edge the end with the longer list is the pivot, its list goes into an LDS hash table
+ * (2048 entries at a time; a longer list in slices) and the other end's list is streamed past it, 16 bytes a lane.  A
+ * found triangle credits its three corners in registers and in 32-bit LDS counters beside the table's slots, which are
+ * flushed with one 64-bit integer atomic add per non-zero slot: no global atomic per triangle and no floating-point
+ * atomic.  Pivots with lists of up to 256 entries are a wave's task, longer ones a workgroup's, 256 / 1024 partners a
+ * task; the task lists come from counts, one scan and a fill.  Everything is carved from one allocation before the first
+ * kernel and freed before the call returns; the host reads one record.  Working memory: 12.1 bytes per stored entry
+ * (directed == 1: 24.2) and 88 bytes per vertex.  A matrix with 2 nvals (directed == 0: nvals) + 4 n >= 2^32 - 16 is
+ * beyond the 32-bit positions of that memory: GRB_OUT_OF_MEMORY.
+ *
+ * Every error is found before lcc is written, and lcc keeps what it held.  A null lcc or A, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, or size(lcc) != n: GRB_DIMENSION_MISMATCH; directed outside {0, 1}:
+ * GRB_INVALID_VALUE; lcc not f32, or A outside f32 / i32: GRB_NOT_IMPLEMENTED; directed == 1 and an A without a CSC of its
+ * own: GRB_INVALID_OBJECT; directed == 0 and an A whose CSC differs from its CSR: GRB_INVALID_VALUE; a failed device
+ * allocation: GRB_OUT_OF_MEMORY.  n = 0, or an A without off-diagonal entries, is a success: all zeros and a zero record. */
+typedef struct {
+  int64_t edges;              /* unordered pairs {u, v}, u != v, joined in either direction                            */
+  int64_t triangles;          /* triangles of that undirected graph                                                    */
+  int64_t closed;             /* sum of num(v) over all v                                                              */
+  int64_t wedges;             /* sum of d(v) (d(v) - 1) over all v; closed / wedges is the transitivity                */
+  int32_t max_degree;         /* largest d(v)                                                                          */
+  float   loop_ms;            /* HIP-event time of the call's device work                                              */
+} grb_lcc_result;
+grb_info grb_lcc(grb_vector lcc, grb_matrix A, int directed, grb_descriptor desc, grb_lcc_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
