@@ -53,6 +53,11 @@ class LccResult(C.Structure):
                 ("max_degree", C.c_int32), ("loop_ms", C.c_float)]
 
 
+class KcoreResult(C.Structure):
+    _fields_ = [("edges", C.c_int64), ("result_edges", C.c_int64), ("kmax", C.c_int32), ("levels", C.c_int32),
+                ("result_vertices", C.c_int32), ("rounds", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -218,6 +223,8 @@ _SIGS = {
     "grb_cdlp": [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(CdlpResult)],
     "grb_cdlp_set_skip": [_i],
     "grb_lcc": [_vp, _vp, _i, _vp, C.POINTER(LccResult)],
+    "grb_coreness": [_vp, _vp, _vp, C.POINTER(KcoreResult)],
+    "grb_kcore": [_vp, _vp, _i, _vp, C.POINTER(KcoreResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

@@ -799,6 +799,40 @@ def lcc(v, A, desc, directed=False):
                       max_degree=res.max_degree, loop_ms=res.loop_ms)
 
 
+def _kcore_dict(res):
+    return dict(edges=res.edges, result_edges=res.result_edges, kmax=res.kmax, levels=res.levels,
+                result_vertices=res.result_vertices, rounds=res.rounds, launches=res.launches, loop_ms=res.loop_ms)
+
+
+def coreness(v, A, desc):
+    """grb_coreness: v = the core number of every vertex of A's graph.  A is n x n, f32 or i32, with the same structure as
+    its transpose; its values are never read (stored zeros are edges) and its diagonal takes no part.  The k-core is the
+    largest subgraph in which every vertex has at least k neighbours inside the subgraph, core(x) = the largest k such that
+    x is in the k-core (0 for an isolated vertex) and kmax = max core(x) is the degeneracy.  v is an i32 vector of size n and
+    becomes dense; the same inputs give the same bits.  The whole peel is one launch on the device.  Only the CSR is read:
+    with a CSC of its own an asymmetric A -> GrB_INVALID_VALUE, without one (a product result, the CSR-only format) the
+    caller vouches for it.  A null or unbuilt argument -> GrB_UNINITIALIZED_OBJECT; A not square or v not of size n ->
+    GrB_DIMENSION_MISMATCH; v not i32 or A outside f32 / i32 -> GrB_NOT_IMPLEMENTED; a grid barrier that gave up ->
+    GrB_PANIC (v unchanged on every error).  Returns (info, dict(edges, result_edges = edges inside the kmax-core, kmax,
+    levels = distinct core numbers, result_vertices = vertices with core(x) == kmax, rounds = grid-wide passes of the
+    device, launches, loop_ms))."""
+    res = _lib.KcoreResult()
+    info = _lib.load().grb_coreness(_h(v), _h(A), _h(desc), C.byref(res))
+    return info, _kcore_dict(res)
+
+
+def kcore(v, A, k, desc):
+    """grb_kcore: v = the k-core of A's graph (A and the definition as for coreness): v[x] = the number of x's neighbours
+    inside the k-core when x is in it (that is >= k), 0 when it is not; the vertex analogue of ktruss storing supports.
+    k = 0 gives the plain degrees, k > kmax all zeros.  v is an i32 vector of size n and becomes dense; the same inputs give
+    the same bits.  k < 0 -> GrB_INVALID_VALUE; the other error codes as for coreness (v unchanged on every error).
+    Returns (info, dict(edges, result_edges = edges inside the k-core, kmax = k, levels = 1, result_vertices = vertices of
+    the k-core, rounds, launches, loop_ms))."""
+    res = _lib.KcoreResult()
+    info = _lib.load().grb_kcore(_h(v), _h(A), int(k), _h(desc), C.byref(res))
+    return info, _kcore_dict(res)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

@@ -1025,6 +1025,65 @@ typedef struct {
 } grb_lcc_result;
 grb_info grb_lcc(grb_vector lcc, grb_matrix A, int directed, grb_descriptor desc, grb_lcc_result* result);
 
+/* The k-core decomposition (csrc/kcore.hip): grb_coreness and grb_kcore.  The reference has no such driver
+ * (graphblas/algorithm/), so the definition is this header's own; it is LAGraph's and Gunrock's, and the vertex counterpart
+ * of grb_trussness / grb_ktruss.
+ *
+ * A is n x n, f32 or i32, with the same structure as its transpose.  Stored values are never read: a stored zero is an
+ * edge.  Diagonal entries take no part.
+ *   G       = the simple undirected graph of A's off-diagonal entries
+ *   d(v)    = v's degree in G
+ *   k-core  = for k >= 0 the largest subgraph of G in which every vertex has at least k neighbours inside the subgraph; it
+ *             is unique
+ *   core(v) = the largest k such that v is in the k-core
+ *   kmax    = max core(v), the degeneracy; 0 for a graph without edges.
+ *
+ * grb_coreness(core, A, desc, result): core is an i32 vector of size n; it becomes dense with all n values stored: core(v),
+ * and 0 for an isolated vertex.
+ * grb_kcore(v, A, k, desc, result): v is an i32 vector of size n; it becomes dense.  v(x) = the number of x's neighbours
+ * inside the k-core when x is in it (that is >= k), and 0 when it is not: the vertex analogue of grb_ktruss storing
+ * supports.  k = 0 gives the plain degrees; k > kmax is a success with all zeros and result_vertices = 0.
+ * Both: desc may be NULL; no descriptor field is read.  result may be NULL.  The same inputs give the same bits: core numbers
+ * and in-core degrees are unique, so this holds whatever order the device peels in.  rounds is the one field that may
+ * depend on scheduling.
+ *
+ * Structure (the rule of grb_lcc with directed == 0): only the CSR is read.  When A has a CSC of its own the symmetry is
+ * checked by one comparison on the device before the peel, and an asymmetric A is GRB_INVALID_VALUE.  An A without a CSC of
+ * its own (a product result, the CSR-only matrix format) is taken on the caller's word: nothing is read or written out of
+ * bounds whatever its structure is, and the values are then unspecified.
+ *
+ * How: the peel loop lives on the device, in ONE co-resident launch of a 1024-thread workgroup per CU whose passes are
+ * separated by a grid barrier with bounded spins; the host reads one record at the end, so launches does not grow with
+ * the rounds or the levels.  State: the current degrees (row length minus a stored diagonal) and ONE queue that holds
+ * every vertex in the order of its removal -- the frontier of a round is the part of it the round before appended.  A
+ * level is the smallest degree left: the pass that lists a level's first frontier also takes the minimum, the number and
+ * the degree sum of the vertices left, so an empty level costs nothing and the vertices left when the last level opens
+ * are the kmax-core.  Removing a vertex walks its row (a lane for rows of up to 8 entries, a wave with 16-byte index
+ * loads up to 2048, the workgroup beyond): a neighbour whose degree is still above the level gets one returning integer
+ * atomic decrement; the thread that sees level + 1 come back appends it, a thread that sees less undoes its decrement,
+ * so a degree never settles below its vertex's level and every vertex is appended exactly once.  Appends are staged per
+ * wave in LDS and reserved with one atomic per batch.  grb_kcore is the same kernel with the one level k - 1 and a last
+ * pass that zeroes what fell.  Working memory: 8 bytes per vertex and 2.25 KiB, one allocation made before the first kernel
+ * and freed before the call returns; nothing is allocated inside the loop.
+ *
+ * Every error is found before the output is written, and the output keeps what it held.  A null output or A, or an unbuilt
+ * A: GRB_UNINITIALIZED_OBJECT; A not square, or size(output) != n: GRB_DIMENSION_MISMATCH; k < 0: GRB_INVALID_VALUE; output
+ * not i32, or A outside f32 / i32: GRB_NOT_IMPLEMENTED; an A whose own CSC differs from its CSR: GRB_INVALID_VALUE; a failed
+ * device allocation: GRB_OUT_OF_MEMORY; a grid barrier that gave up: GRB_PANIC, as in the other one-launch drivers.  n = 0,
+ * or an A without off-diagonal entries, is a success: all zeros, kmax = 0, and levels = 1 when n > 0. */
+typedef struct {
+  int64_t edges;            /* undirected edges of G                                                               */
+  int64_t result_edges;     /* grb_coreness: edges inside the kmax-core; grb_kcore: edges inside the k-core        */
+  int32_t kmax;             /* grb_coreness: the degeneracy; grb_kcore: the k given                                */
+  int32_t levels;           /* grb_coreness: distinct values of core(v); grb_kcore: 1                              */
+  int32_t result_vertices;  /* grb_coreness: vertices with core(v) == kmax; grb_kcore: vertices of the k-core      */
+  int32_t rounds;           /* grid-wide peeling passes the device ran: implementation-defined, for the bench only */
+  int32_t launches;         /* kernel launches of the peel itself: 1                                               */
+  float   loop_ms;          /* HIP-event time of the call's device work                                            */
+} grb_kcore_result;          /* 40 bytes */
+grb_info grb_coreness(grb_vector core, grb_matrix A, grb_descriptor desc, grb_kcore_result* result);
+grb_info grb_kcore(grb_vector v, grb_matrix A, int k, grb_descriptor desc, grb_kcore_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
