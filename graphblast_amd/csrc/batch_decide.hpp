@@ -41,6 +41,7 @@ struct BatchDecision {
   unsigned long long qmask, pmask;   // bits pulled / pushed
   double pushed_edges;               // the out-edges of the pushed sources
   int kind;                          // BatchDecideKind
+  unsigned long long stash;          // a heavy host level: pmask (batch_decide_stash), else 0
 };
 
 // source s is live and under the switch point: pushed, if the budget allows
@@ -75,6 +76,15 @@ GRB_DECIDE_HD inline int batch_decide_kind(unsigned long long qmask, unsigned lo
   return kDecideHost;
 }
 
+// A host level is HEAVY when its pushed sources bring more out-edges than half the vertices: the push kernels then only
+// claim in `seen`, and the commit pass tells the new bits from the old by the pushed sources' old seen-bits, which the
+// pull pass in front has stashed in the level's own words.  `stash` = the bit columns that carry them: pmask on a heavy
+// level of the host loop, 0 on every other level.  pushed_edges is an integer below 2^53 whoever summed it.
+GRB_DECIDE_HD inline bool batch_decide_heavy(double pushed_edges, long long n) { return pushed_edges > 0.5 * (double)n; }
+GRB_DECIDE_HD inline unsigned long long batch_decide_stash(unsigned long long pmask, double pushed_edges, long long n, int kind) {
+  return kind == kDecideHost && pmask != 0 && batch_decide_heavy(pushed_edges, n) ? pmask : 0ull;
+}
+
 GRB_DECIDE_HD inline BatchDecision batch_decide(const unsigned long long* nf_s, const unsigned long long* mf_s,
                                                 const BatchRule& r, bool iteration_left) {
   BatchDecision d;
@@ -88,6 +98,7 @@ GRB_DECIDE_HD inline BatchDecision batch_decide(const unsigned long long* nf_s, 
     if (w == 1) { d.pmask |= 1ull << s; d.pushed_edges += (double)mf_s[s]; }
   }
   d.kind = batch_decide_kind(d.qmask, d.pmask, d.pushed_edges, r, iteration_left);
+  d.stash = batch_decide_stash(d.pmask, d.pushed_edges, r.n, d.kind);
   return d;
 }
 

@@ -45,9 +45,17 @@ constexpr int kBatchSlots = 16;       // counter slots (spreads same-address ato
 constexpr int kBatchStoreMax = 16;    // level words kept for the final label pass
 constexpr int kBatchCounters = 2 + 128 + 1;   // per slot: vertices, the big in-rows still open (below), {nf_s, mf_s} per source, big out-rows found
 constexpr int kCntInOpen = 1, kCntBigOut = 2 + 128;
-constexpr int kBatchBoxPer = kBatchCounters + 8;      // the host's box: where the light-level launch leaves TailState::cum and ::last
-constexpr int kBoxDecision = kBatchCounters + 5;      // box: {qmask, pmask, kind} of the NEXT level, as batch_totals_kernel decided it
-constexpr int kBatchCtlWords = 4;                     // the device's copy of the same three, behind the counter slots; [3]: the last light-level launch's status
+constexpr int kBatchBoxPer = kBatchCounters + 9;      // the host's box: where the light-level launch leaves TailState::cum and ::last
+constexpr int kBoxDecision = kBatchCounters + 5;      // box: {qmask, pmask, kind, stash} of the NEXT level, as batch_totals_kernel decided it
+constexpr int kBatchCtlWords = 5;                     // the device's copy of the first three, behind the counter slots; [3]: the last light-level launch's status; [4]: stash
+constexpr int kCtlStash = 4;
+// The big-row list of an owner-computes level is kept in kListSegs parts, each with a length on a line of its own: a wave
+// of batch_push_kernel appends to part (workgroup index mod kListSegs).  With ONE length the ~1500 waves that list a row
+// at RMAT-22 queued behind one address (5 ns an update: 7 us on the push kernel, measured); the owners read the parts
+// end to end.
+constexpr int kListSegs = 8;
+constexpr int kListLenStride = 32;                    // unsigned ints between two lengths: 128 bytes
+constexpr size_t kListHeader = (size_t)kListSegs * kListLenStride * sizeof(unsigned int);
 // counter kCntInOpen: the big in-rows that still lack a bit of some source (fewer than 2^31: a row index is an int), with
 // bit 62 set when the level's batch_big_apply_kernel counted them at all; counter kCntBigOut: the vertices with a new bit
 // whose out-row is big
@@ -66,7 +74,12 @@ struct BatchArgs {
   u64* fnext;
   int big;                            // rows of this many entries or more belong to the slice kernels
   int big_out;                        // ... the same for out-rows, whichever direction the kernel works in: what batch_commit_l counts
-  const u64* prev;                    // heavy push levels: seen as it stood before the push kernels (else null)
+  int claims;                         // heavy push levels: the push kernels claim in seen and nothing else; the commit pass finds the new bits
+  u64 stash;                          // the bit columns of fnext that carry the pushed sources' OLD seen-bits from the pull pass to the commit
+                                      // pass: pmask on a heavy level, else 0 (batch_decide_stash)
+  const int* big_index;               // batch_push_kernel on an owner-computes level: vertex -> big index, for the list (else null)
+  int* list;                          // ... the list it appends the skipped big frontier rows to: {big index, pushed frontier bits}, part g at g * nbig
+  u64* list_fw;
   const int4* slices;                 // {vertex, first entry, end entry, big index}
   int nslices;
   const Index* bigrows;               // the big rows' vertex ids
@@ -75,8 +88,9 @@ struct BatchArgs {
   float new_label;
   int direct_labels;                  // levels beyond the stored ones write labels as they discover
   int k;
-  unsigned int* list_len;             // batch_push_commit_kernel behind the owner kernels: the big-row list's length, reset for the next level (else null)
-  const u64* ctl;                     // a launch made ahead of the host: {qmask, pmask, kind} as the level before decided them (else null)
+  unsigned int* list_len;             // the big-row list's kListSegs lengths (kListLenStride apart): appended to by batch_push_kernel, put back to
+                                      // zero for the next level by batch_push_commit_kernel behind the owner kernels (else null)
+  const u64* ctl;                     // a launch made ahead of the host: {qmask, pmask, kind, -, stash} as the level before decided them (else null)
   float* label[64];
 };
 
@@ -94,12 +108,18 @@ __device__ inline u64 wave_or(u64 x) { return wave_or_u64(x); }   // DPP (common
 
 // the bits a pull kernel works on; false: launched ahead of a level that turned out to be none of the host loop's --
 // nothing is read or written (grid-uniform: every workgroup leaves before its first barrier)
-__device__ inline bool batch_pull_bits(const BatchArgs& a, u64& q) {
+__device__ inline bool batch_pull_bits(const BatchArgs& a, u64& q, u64& stash) {
   q = a.qmask;
+  stash = a.stash;
   if (!a.ctl) return true;
   if (a.ctl[2] != (u64)kDecideHost) return false;
   q = a.ctl[0];
+  stash = a.ctl[kCtlStash];
   return true;
+}
+__device__ inline bool batch_pull_bits(const BatchArgs& a, u64& q) {
+  u64 stash;
+  return batch_pull_bits(a, q, stash);
 }
 
 struct BatchTotals {                  // per workgroup, in LDS
@@ -272,10 +292,15 @@ __global__ __launch_bounds__(kBlock) void batch_pull_kernel(BatchArgs a) {
   __shared__ Index s_pre[kWavesPerBlock][kWave];
   __shared__ Index s_p[kWavesPerBlock][kWave];
   __shared__ u64 s_acc[kWavesPerBlock][kWave];
-  u64 qmask;
-  if (!batch_pull_bits(a, qmask)) return;
+  // Heavy level (stash = pmask != 0): every store of the level's word also carries the vertex's OLD seen-bits of the
+  // pushed sources, in their own bit columns -- disjoint from qmask, so batch_pull_slices_kernel and
+  // batch_big_apply_kernel, which mask what they read of fnext with qmask, never see them; the push kernels of such a
+  // level do not touch fnext, and batch_push_commit_kernel takes the columns back (new = seen & pmask & ~stashed).
+  u64 qmask, stash;
+  if (!batch_pull_bits(a, qmask, stash)) return;
   if (qmask == 0) {                                         // every live source is pushed: the push kernels OR into all-zero words
-    for (Index v = (Index)blockIdx.x * blockDim.x + threadIdx.x; v < a.n; v += (Index)gridDim.x * blockDim.x) a.fnext[v] = 0ull;
+    for (Index v = (Index)blockIdx.x * blockDim.x + threadIdx.x; v < a.n; v += (Index)gridDim.x * blockDim.x)
+      a.fnext[v] = stash ? (a.seen[v] & stash) : 0ull;      // (grid-uniform: seen is read on a heavy level only)
     return;
   }
   totals_init(&lds);
@@ -293,7 +318,7 @@ __global__ __launch_bounds__(kBlock) void batch_pull_kernel(BatchArgs a) {
     const bool big = e - p >= a.big;                       // probed here, finished by the slice kernels
     if (p == e) need = 0;
     if (__ballot(need != 0) == 0ull) {
-      if (valid) a.fnext[v] = 0ull;
+      if (valid) a.fnext[v] = seen & stash;
       continue;
     }
     u64 acc = 0;
@@ -351,7 +376,7 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
     }
     const u64 newb = acc & need;
     if (valid) {
-      a.fnext[v] = newb;                                   // a big row's probe result: the slices add to it,
+      a.fnext[v] = newb | (seen & stash);                  // a big row's probe result: the slices add to it,
       if (newb && !big) a.seen[v] = seen | newb;           // batch_big_apply_kernel claims and counts it
     }
     batch_commit(a, tot, valid ? v : 0, big ? 0ull : newb);
@@ -420,9 +445,9 @@ __device__ inline void batch_push_slots(const BatchArgs& a, const Index* __restr
   for (int j = 0; j < N; ++j) dst[j] = q[j] >= 0 ? ind[q[j]] : -1;
 #pragma unroll
   for (int j = 0; j < N; ++j) bits[j] = dst[j] >= 0 ? (fw[j] & ~a.seen[dst[j]]) : 0ull;
-  if (a.prev) {
+  if (a.claims) {
     // heavy level: the claim alone, fire and forget -- one random line per edge; the commit pass finds the
-    // claimed bits as seen & ~prev
+    // claimed bits as seen & pmask & ~(the old bits stashed in fnext)
 #pragma unroll
     for (int j = 0; j < N; ++j)
       if (bits[j]) atomicOr(&a.seen[dst[j]], bits[j]);
@@ -452,7 +477,22 @@ __global__ __launch_bounds__(kBlock) void batch_push_kernel(BatchArgs a) {
     if (__ballot(fw != 0) == 0ull) continue;
     Index p = 0, e = 0;
     if (fw) { p = a.optr[u]; e = a.optr[u + 1]; }
-    if (e - p >= a.big) p = e;                             // the slice kernel expands it
+    const bool skipped = e - p >= a.big;                   // the slice kernel, or the owners, expand it
+    if (skipped) p = e;
+    if (a.big_index) {                                     // owner-computes level: the owners' list, one length update per wave
+      const unsigned long long m = __ballot(skipped);
+      if (m) {
+        const unsigned int seg = blockIdx.x & (kListSegs - 1);
+        unsigned int b0 = 0;
+        if (lane == 0) b0 = atomicAdd(&a.list_len[seg * kListLenStride], (unsigned int)__popcll(m));
+        b0 = __shfl(b0, 0, kWave);
+        if (skipped) {                                     // (a part holds at most every big row once: nbig entries)
+          const size_t at = (size_t)seg * (size_t)a.nbig + b0 + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+          a.list[at] = a.big_index[u];
+          a.list_fw[at] = fw;                              // the owners read (row, bits) in one step, not three
+        }
+      }
+    }
     const Index d = e - p;
     Index inc = d;
 inc = (Index)wave_incl_scan_u32((unsigned)inc);
@@ -539,25 +579,10 @@ __global__ void batch_range_off_kernel(const Index* __restrict__ optr, const Ind
   }
 }
 
-__global__ __launch_bounds__(kBlock) void batch_big_list_kernel(BatchArgs a, int* __restrict__ list, u64* __restrict__ list_fw,
-                                                                unsigned int* __restrict__ count) {
-  const int lane = lane_id();
-  for (int base = (blockIdx.x * kWavesPerBlock + wave_id()) * kWave; base < a.nbig; base += gridDim.x * kBlock) {
-    const int bi = base + lane;
-    const u64 fw = bi < a.nbig ? (a.fcur[a.bigrows[bi]] & a.pmask) : 0ull;
-    const unsigned long long m = __ballot(fw != 0ull);
-    if (!m) continue;
-    unsigned int b0 = 0;
-    if (lane == 0) b0 = atomicAdd(count, (unsigned int)__popcll(m));
-    b0 = __shfl(b0, 0, kWave);
-    if (fw) {
-      const unsigned int at = b0 + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
-      list[at] = bi;
-      list_fw[at] = fw;                                    // the owners read (row, bits) in one step, not three
-    }
-  }
-}
-
+// The list of a level's big frontier rows, {big index, pushed frontier bits}, is written by batch_push_kernel, which
+// reads every frontier word and every frontier row's extent anyway and skips exactly these rows (BatchArgs::big_index:
+// the per-matrix table vertex -> big index), in kListSegs parts; batch_push_commit_kernel, behind the owners, puts their
+// lengths back to zero.
 // A power-law graph sends a fifth of all edges to its first 16 Ki vertices: the ranges are cut at equal in-degree
 // mass (at most 8 Ki rows each), so the hub region is many narrow ranges.  (Equal-width ranges with the heavy ones
 // shared between several workgroups -- each with its own LDS copy, written back with atomicOr -- were measured
@@ -580,14 +605,26 @@ __global__ __launch_bounds__(kThreads) void batch_push_owner_kernel(BatchArgs a,
   const int rows = (int)(bounds[b + 1] - base);
   for (int i = tid; i < rows; i += kThreads) acc[i] = 0ull;
   __syncthreads();
-  const long long nlist = (long long)*count;
+  // where each part of the list starts when they are laid end to end: wave-uniform, kept in scalar registers (the wide
+  // instance's LDS is exactly half a CU's: a word more and one workgroup fits where two did)
+  unsigned int seg0[kListSegs + 1];
+  seg0[0] = 0u;
+#pragma unroll
+  for (int g = 0; g < kListSegs; ++g) seg0[g + 1] = seg0[g] + count[g * kListLenStride];
+  const long long nlist = (long long)seg0[kListSegs];
   for (long long k0 = 0; k0 < nlist; k0 += kThreads) {
     const long long i = k0 + tid;
     Index o0 = 0, o1 = 0;
     u64 fw = 0ull;
     if (i < nlist) {
-      const int bi = list[i];
-      fw = list_fw[i];
+      int g = 0;                                            // the last part that starts at or before i (never an empty one)
+      unsigned int g0 = 0u;
+#pragma unroll
+      for (int t = 1; t < kListSegs; ++t)
+        if (seg0[t] <= (unsigned int)i) { g = t; g0 = seg0[t]; }
+      const size_t at = (size_t)g * (size_t)a.nbig + (size_t)((unsigned int)i - g0);
+      const int bi = list[at];
+      fw = list_fw[at];
       o0 = range_off[(size_t)bi * S + b];                   // neighbours: one line per list entry
       o1 = range_off[(size_t)bi * S + b + 1];
     }
@@ -634,16 +671,19 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
     const u64 x = acc[i];
     if (x != 0ull) {
       const u64 sv = a.seen[v];
-      if (x & ~sv) a.seen[v] = sv | x;                     // the claim; the commit pass finds it as seen & ~prev
+      if (x & ~sv) a.seen[v] = sv | x;                     // the claim; the commit pass finds it against the stashed old bits
     }
   }
 }
 
-// after the push kernels of a level: the pushed bits that arrived in fnext are this level's discoveries
+// after the push kernels of a level: the pushed bits that arrived in fnext are this level's discoveries.  Heavy level
+// (claims only): fnext's P columns hold the pushed sources' seen-bits as the pull pass found them, so what the push
+// kernels claimed is seen & P & ~old; the columns are rewritten with exactly that -- every stashed bit is cleared, and
+// the level's words are the discoveries again before the next level or the label pass reads them.
 __global__ __launch_bounds__(kBlock) void batch_push_commit_kernel(BatchArgs a) {
   __shared__ BatchTotals lds;
   totals_init(&lds);
-  if (a.list_len && blockIdx.x == 0 && threadIdx.x == 0) *a.list_len = 0u;   // the owner kernels in front of this launch have read it
+  if (a.list_len && blockIdx.x == 0 && threadIdx.x < kListSegs) a.list_len[threadIdx.x * kListLenStride] = 0u;   // the owner kernels in front of this launch have read them
   WaveTotals tot;
   const int lane = lane_id();
   const Index nchunks = (a.n + kWave - 1) / kWave;
@@ -652,9 +692,10 @@ __global__ __launch_bounds__(kBlock) void batch_push_commit_kernel(BatchArgs a) 
     const Index v = chunk * kWave + lane;
     u64 pb = 0;
     if (v < a.n) {
-      if (a.prev) {
-        pb = a.seen[v] & ~a.prev[v];
-        if (pb) a.fnext[v] |= pb;
+      if (a.claims) {
+        const u64 w = a.fnext[v], old = w & a.pmask;
+        pb = a.seen[v] & a.pmask & ~old;
+        if (old | pb) a.fnext[v] = (w & ~a.pmask) | pb;
       } else {
         pb = a.fnext[v] & a.pmask;
       }
@@ -727,10 +768,12 @@ __global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64
     const u64 pushed = wave_sum_u64(way == 1 ? s_mf[i] : 0ull);   // integers below 2^53: the host's sum of doubles is the same number
     if (i == 0) {
       const u64 kind = (u64)batch_decide_kind(q, p, (double)pushed, d.rule, d.iteration_left != 0);
-      d.ctl[0] = q; d.ctl[1] = p; d.ctl[2] = kind;
+      const u64 stash = batch_decide_stash(p, (double)pushed, d.rule.n, (int)kind);
+      d.ctl[0] = q; d.ctl[1] = p; d.ctl[2] = kind; d.ctl[kCtlStash] = stash;
       __hip_atomic_store(&box[kBoxDecision], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&box[kBoxDecision + 1], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&box[kBoxDecision + 2], kind, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(&box[kBoxDecision + 3], stash, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
   __threadfence_system();
@@ -1144,6 +1187,7 @@ static grb_info ensure_slices(grb_matrix A, bool in_edges) {
     if (B.d_range_off) (void)hipFree(B.d_range_off);
     if (B.d_range_bounds) (void)hipFree(B.d_range_bounds);
     if (B.d_range_ids) (void)hipFree(B.d_range_ids);
+    if (B.d_big_index) (void)hipFree(B.d_big_index);
     B = BatchSlices();
   }
   return i;
@@ -1215,6 +1259,11 @@ static grb_info make_slices(grb_matrix A, bool in_edges) {
         }
         GRB_HIP_TRY(hipMalloc((void**)&B.d_range_ids, sizeof(int) * ids.size()));
         GRB_HIP_TRY(hipMemcpy(B.d_range_ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice));
+        // vertex -> big index: batch_push_kernel lists the big frontier rows it skips by it (read for big rows only)
+        std::vector<int> big_index((size_t)n, -1);
+        for (size_t bi = 0; bi < rows.size(); ++bi) big_index[(size_t)rows[bi]] = (int)bi;
+        GRB_HIP_TRY(hipMalloc((void**)&B.d_big_index, sizeof(int) * (size_t)n));
+        GRB_HIP_TRY(hipMemcpy(B.d_big_index, big_index.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
       }
     }
   }
@@ -1283,8 +1332,8 @@ static SweepSizes sweep_sizes(grb_matrix A) {
   z.qcap = (size_t)n + (size_t)(A->nvals / kTailPiece) + 64;
   z.tail_state = (sizeof(TailState) + 255) & ~(size_t)255;
   z.tail = kTailStates * z.tail_state + 3 * sizeof(u64) * z.qcap;
-  z.list_ids = (sizeof(int) * (size_t)A->batch_out.nbig + 255) & ~(size_t)255;
-  z.list = 256 + z.list_ids + sizeof(u64) * (size_t)A->batch_out.nbig;
+  z.list_ids = (sizeof(int) * (size_t)kListSegs * (size_t)A->batch_out.nbig + 255) & ~(size_t)255;
+  z.list = kListHeader + z.list_ids + sizeof(u64) * (size_t)kListSegs * (size_t)A->batch_out.nbig;
   return z;
 }
 
@@ -1329,8 +1378,8 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   u64* seen = (u64*)p_words;
   // level words: slot 0 .. nstore are kept for the label pass (which level each holds is recorded as it is taken; slot 0
   // the seeds, or level 1 when the first level is the plain launch);
-  // four more rotate -- a level beyond the kept ones (it labels as it discovers), the copy of `seen` a heavy push
-  // compares against, the three word arrays of the light-level launch
+  // four more rotate -- a level beyond the kept ones (it labels as it discovers) and the three word arrays of the
+  // light-level launch
   auto Slot = [&](int i) -> u64* { return seen + (size_t)(1 + i) * (size_t)n; };
   u64* const pool[4] = {Slot(nstore + 1), Slot(nstore + 2), Slot(nstore + 3), Slot(nstore + 4)};
   // known all-zero: the light-level launch leaves its arrays so, and the knowledge survives to the next sweep if nobody
@@ -1373,6 +1422,8 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   a.k = k;
   a.ctl = nullptr;
   a.list_len = nullptr;
+  a.claims = 0; a.stash = 0;
+  a.big_index = nullptr; a.list = nullptr; a.list_fw = nullptr;
   a.big_out = batch_big(false);
   u64* const d_ctl = a.counters + kBatchSlots * kBatchCounters;   // written by every totals kernel before anybody reads it
   for (int s = 0; s < 64; ++s) a.label[s] = nullptr;
@@ -1391,7 +1442,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   unsigned int* const d_count = (unsigned int*)p_list;
   if (!(own && own->small_clean)) {
     GRB_HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
-    GRB_HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
+    GRB_HIP_TRY(hipMemsetAsync(d_count, 0, kListHeader, st));
   }
   if (own) own->small_clean = false;
   // the light-level launches' state blocks, all of them now: the fill runs while the host is still enqueuing the sweep's
@@ -1542,10 +1593,11 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     const u64 P = dec.pmask, Q = dec.qmask;
     const double pushed_edges = dec.pushed_edges;
     a.qmask = Q; a.pmask = P;
-    a.prev = nullptr;
+    a.claims = 0; a.stash = 0;
     a.fcur = fcur_words;
     a.ctl = nullptr;
     a.list_len = nullptr;
+    a.big_index = nullptr; a.list = nullptr; a.list_fw = nullptr;
     // ---- every live source pushed and few edges to push: this level and the light ones after it in one launch
     if (dec.kind == kDecideLight) {
       pulled_ahead = false;                                 // (launched ahead, the pull kernels found this out and wrote nothing: the plan is dropped)
@@ -1625,6 +1677,10 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     a.new_label = (float)(iter + 1);
     a.direct_labels = slot.keep ? 0 : 1;
     const bool plain_level = first_plain && iter == 1;
+    // heavy: as whoever decided the level published it (the totals kernel, or batch_decide here) -- never derived a second
+    // time, the pull kernels launched ahead have already stashed by it.  The first level's plain launch claims directly.
+    const bool heavy = dec.stash != 0 && !plain_level;
+    a.stash = heavy ? dec.stash : 0ull;
     if (plain_level) {
       // the sources' rows, a wave per piece, into Slot(0): the fill at the sweep's start has zeroed it
       FirstPieces fp;
@@ -1636,6 +1692,11 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       // the pull kernels are already running, or done: for Q == 0 they have zeroed the words
     } else if (Q) {
       GRB_TRY(launch_pull(a));
+    } else if (heavy) {
+      // nothing pulled, but the stash is wanted: the pull kernel's qmask == 0 path writes seen & stash where the fill
+      // wrote zeros (it reads no CSC array, so a push-only matrix takes it too)
+      hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+      GRB_HIP_TRY(hipGetLastError());
     } else {
       GRB_HIP_TRY(hipMemsetAsync(a.fnext, 0, sizeof(u64) * (size_t)n, st));
     }
@@ -1643,41 +1704,55 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     if (P && !plain_level) {
       const BatchSlices& B = A->batch_out;
       a.big = batch_big(false);
-      if (pushed_edges > 0.5 * (double)n) {                 // heavy: claims only, the new bits read back against a copy
-        const int pi = pick(fcur_words, a.fnext, nullptr, false);
-        u64* prev = pool[pi];
-        pool_clean[pi] = false;
-        GRB_HIP_TRY(hipMemcpyAsync(prev, seen, sizeof(u64) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        a.prev = prev;
-      }
+      a.claims = heavy ? 1 : 0;                             // claims only: the new bits are read back against the stashed old ones
       a.slices = B.d_slices; a.nslices = B.nslices; a.bigrows = B.d_rows; a.nbig = B.nbig;
-      const bool big_rows = B.nslices > 0 && big_out_new != 0;   // none in the frontier: no slice, list or owner kernel has anything to do
+      const bool big_rows = B.nslices > 0 && big_out_new != 0;   // none in the frontier: no slice or owner kernel has anything to do
+      static const bool owner_ok = [] { const char* e = getenv("GRB_BATCH_OWNER"); return !e || atoi(e) != 0; }();
+      static const bool owner_merge = [] { const char* e = getenv("GRB_BATCH_OWNER_MERGE"); return !e || atoi(e) != 0; }();
+      const bool owners = big_rows && heavy && owner_ok && B.d_range_off && B.d_big_index;
+      int* d_list = (int*)((char*)p_list + kListHeader);
+      u64* d_list_fw = (u64*)((char*)p_list + kListHeader + z.list_ids);
+      if (owners) {
+        // heavy level: the big rows' edges are settled by the owners of their destination ranges, in LDS; the push kernel
+        // lists the big frontier rows it skips
+        a.big_index = B.d_big_index; a.list = d_list; a.list_fw = d_list_fw;
+        a.list_len = d_count;                                // zero here; the commit kernel below puts it back to zero
+      }
       hipLaunchKernelGGL(batch_push_kernel, dim3(grid), dim3(kBlock), 0, st, a);
       GRB_HIP_TRY(hipGetLastError());
-      static const bool owner_ok = [] { const char* e = getenv("GRB_BATCH_OWNER"); return !e || atoi(e) != 0; }();
-      if (big_rows && a.prev && owner_ok && B.d_range_off) {
-        // heavy level: the big rows' edges are settled by the owners of their destination ranges, in LDS
-        const size_t list_bytes = z.list_ids;
-        int* d_list = (int*)((char*)p_list + 256);
-        u64* d_list_fw = (u64*)((char*)p_list + 256 + list_bytes);
-        a.list_len = d_count;                                // zero here; the commit kernel below puts it back to zero
-        hipLaunchKernelGGL(batch_big_list_kernel, dim3(stream_grid(B.nbig, kBlock)), dim3(kBlock), 0, st, a, d_list, d_list_fw, d_count);
-        GRB_HIP_TRY(hipGetLastError());
+      a.big_index = nullptr;
+      if (owners) {
         const int S = (int)own_off_stride(B.nranges);
-        if (B.nsmall > 0)
-          hipLaunchKernelGGL((batch_push_owner_kernel<kOwnSmallRows, 512>), dim3(B.nsmall), dim3(512), 0, st, a, (const Index*)B.d_range_off,
-                             S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
-                             (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
-        if (B.nranges > B.nsmall)
-          hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(B.nranges - B.nsmall), dim3(1024), 0, st, a,
+        // Few narrow ranges (fewer than CUs: a launch of them cannot occupy the chip, whatever its occupancy per CU -- on
+        // RMAT-22 it is ONE workgroup, the hub range, walking its pieces of every listed row for 20 us while the wide
+        // instance waits): one launch of the wide instance over all ranges, which handles a range of <= 2 Ki rows as it
+        // stands.  The ids are taken from their start, narrow ranges first, so the long hub workgroups start first.  The
+        // XCD dealing of make_slices holds up to a rotation: the wide part's eighths land on XCDs rotated by nsmall mod 8,
+        // each still contiguous on one XCD.  GRB_BATCH_OWNER_MERGE=0: always the two launches (A/B runs, tests).
+        const bool merged = owner_merge && B.nsmall > 0 && B.nranges > B.nsmall && B.nsmall < c.num_cu;
+        if (merged) {
+          hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(B.nranges), dim3(1024), 0, st, a,
                              (const Index*)B.d_range_off, S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
-                             (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + B.nsmall);
+                             (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
+        } else {
+          if (B.nsmall > 0)
+            hipLaunchKernelGGL((batch_push_owner_kernel<kOwnSmallRows, 512>), dim3(B.nsmall), dim3(512), 0, st, a, (const Index*)B.d_range_off,
+                               S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                               (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
+          if (B.nranges > B.nsmall)
+            hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(B.nranges - B.nsmall), dim3(1024), 0, st, a,
+                               (const Index*)B.d_range_off, S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
+                               (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + B.nsmall);
+        }
         GRB_HIP_TRY(hipGetLastError());
         if (trace) {
-          unsigned int hc = 0;
-          GRB_HIP_TRY(hipMemcpy(&hc, d_count, 4, hipMemcpyDeviceToHost));
+          unsigned int hc = 0, parts[kListSegs * kListLenStride];
+          GRB_HIP_TRY(hipMemcpy(parts, d_count, kListHeader, hipMemcpyDeviceToHost));
+          for (int g = 0; g < kListSegs; ++g) hc += parts[g * kListLenStride];
           fprintf(stderr, "batch level %d: owner-computes push, %u of %d big rows in the frontier, %d ranges (%d narrow, %d wide)\n", iter, hc, B.nbig,
                   B.nranges, B.nsmall, B.nranges - B.nsmall);
+          const int launches = merged ? 1 : (B.nsmall > 0 ? 1 : 0) + (B.nranges > B.nsmall ? 1 : 0);
+          fprintf(stderr, "batch level %d: range owners in %d launch%s\n", iter, launches, launches == 1 ? "" : "es");
         }
       } else if (big_rows) {
         hipLaunchKernelGGL(batch_push_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
@@ -1702,7 +1777,8 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       an.fnext = planned.fnext;
       an.new_label = (float)(iter + 2);
       an.direct_labels = planned.keep ? 0 : 1;
-      an.prev = nullptr;
+      an.claims = 0; an.stash = 0;
+      an.list_len = nullptr;
       an.qmask = 0; an.pmask = 0;
       an.ctl = d_ctl;
       GRB_TRY(launch_pull(an));
@@ -1714,6 +1790,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     dec.qmask = __atomic_load_n(&h_box[kBoxDecision], __ATOMIC_RELAXED);
     dec.pmask = __atomic_load_n(&h_box[kBoxDecision + 1], __ATOMIC_RELAXED);
     dec.kind = (int)__atomic_load_n(&h_box[kBoxDecision + 2], __ATOMIC_RELAXED);
+    dec.stash = __atomic_load_n(&h_box[kBoxDecision + 3], __ATOMIC_RELAXED);
     have_dec = true;
     if ((t[kCntInOpen] & kInOpenCounted) && (t[kCntInOpen] & (kInOpenCounted - 1)) == 0) in_done = true;
     big_out_new = (long long)t[kCntBigOut];
@@ -1735,7 +1812,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     if (trace)
       fprintf(stderr, "batch level %d: pull %d sources, push %d (%.0f edges, %s) -> vertices %llu pairs %llu, big in-rows open %s%llu, "
               "big out-rows found %lld, next level %s  %.1f us\n",
-              iter, __builtin_popcountll(Q), __builtin_popcountll(P), pushed_edges, a.prev ? "claims" : "direct", t[0],
+              iter, __builtin_popcountll(Q), __builtin_popcountll(P), pushed_edges, a.claims ? "claims" : "direct", t[0],
               pairs, (t[kCntInOpen] & kInOpenCounted) ? "" : "(not counted) ", t[kCntInOpen] & (kInOpenCounted - 1), big_out_new,
               dec.kind == kDecideHost ? (pulled_ahead ? "pulled ahead" : "host") : dec.kind == kDecideLight ? "light" : "none",
               now_us() - t_lvl);
@@ -1801,10 +1878,10 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   a.counters = (u64*)own->cnt;
   a.direct_labels = 1;
   GRB_HIP_TRY(hipMemsetAsync(own->cnt, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
-  GRB_HIP_TRY(hipMemsetAsync(own->list, 0, 256, st));       // the list's length: 0
+  GRB_HIP_TRY(hipMemsetAsync(own->list, 0, kListHeader, st));   // the list's lengths: 0
   unsigned int* d_count = (unsigned int*)own->list;
-  int* d_list = (int*)((char*)own->list + 256);
-  u64* d_list_fw = (u64*)((char*)own->list + 256 + z.list_ids);
+  int* d_list = (int*)((char*)own->list + kListHeader);
+  u64* d_list_fw = (u64*)((char*)own->list + kListHeader + z.list_ids);
   if (!own->warmed) {
     SeedSources none;
     memset(&none, 0, sizeof(none));
@@ -1819,7 +1896,6 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
     hipLaunchKernelGGL(batch_big_apply_kernel, dim3(1), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(batch_push_kernel, dim3(1), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(batch_push_slices_kernel, dim3(1), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(batch_big_list_kernel, dim3(1), dim3(kBlock), 0, st, a, d_list, d_list_fw, d_count);
     hipLaunchKernelGGL(batch_push_commit_kernel, dim3(1), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(batch_unlabel_kernel, dim3(1), dim3(kBlock), 0, st, a, 0.f);
     LabelArgs L;
@@ -1914,9 +1990,10 @@ grb_info grb::bfs_sweep_provision(grb_matrix A) {
     const size_t max_slices = (size_t)(A->nvals / (in ? kBatchSlice : kBatchPushSlice)) + max_rows;
     grow += sizeof(int4) * max_slices + sizeof(Index) * max_rows;
     if (!in) {
-      list_bound = 256 + ((sizeof(int) * max_rows + 255) & ~(size_t)255) + sizeof(u64) * max_rows;   // (the big-row list: SweepSizes::list)
+      list_bound = kListHeader + ((sizeof(int) * kListSegs * max_rows + 255) & ~(size_t)255) + sizeof(u64) * kListSegs * max_rows;   // (the big-row list: SweepSizes::list)
       const size_t max_ranges = (size_t)(3 * 256 + A->nrows / kOwnSmallRows + 2);
       grow += sizeof(Index) * std::min<size_t>(max_rows * (size_t)own_off_stride((long long)max_ranges), (size_t)128 << 20) + 2 * sizeof(Index) * (max_ranges + 1);
+      grow += sizeof(int) * (size_t)A->nrows;                // the table vertex -> big index
     }
   }
   {

@@ -618,6 +618,7 @@ struct BatchSlices {
   Index* d_range_bounds = nullptr;   // [nranges + 1] first destination of each range: equal in-degree mass, at most 16 Ki rows
   int* d_range_ids = nullptr;        // the ranges of at most 2 Ki rows first (nsmall of them), then the wider ones; each group dealt so that an XCD owns a contiguous eighth
   int nsmall = 0;
+  int* d_big_index = nullptr;        // out-edges only, with the ranges: [n] vertex -> its index among the big rows (the rest never read)
 };
 int spmv_reuse_threshold(int set);
 grb_info k_apply_unary(int dtype, int unary, int op, double scalar, const void* in, void* out, Index n);   // elementwise.hip

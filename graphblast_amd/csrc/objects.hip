@@ -842,6 +842,7 @@ void grb::matrix_release_device(grb_matrix A) {
     if (b->d_range_off) (void)hipFree(b->d_range_off);
     if (b->d_range_bounds) (void)hipFree(b->d_range_bounds);
     if (b->d_range_ids) (void)hipFree(b->d_range_ids);
+    if (b->d_big_index) (void)hipFree(b->d_big_index);
     *b = BatchSlices();
   }
   A->sweep_state = 0;
