@@ -58,6 +58,12 @@ class KcoreResult(C.Structure):
                 ("result_vertices", C.c_int32), ("rounds", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
 
 
+class SccResult(C.Structure):
+    _fields_ = [("edges", C.c_int64), ("components", C.c_int32), ("largest", C.c_int32), ("trivial", C.c_int32),
+                ("trimmed", C.c_int32), ("rounds", C.c_int32), ("passes", C.c_int32), ("launches", C.c_int32),
+                ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -225,6 +231,7 @@ _SIGS = {
     "grb_lcc": [_vp, _vp, _i, _vp, C.POINTER(LccResult)],
     "grb_coreness": [_vp, _vp, _vp, C.POINTER(KcoreResult)],
     "grb_kcore": [_vp, _vp, _i, _vp, C.POINTER(KcoreResult)],
+    "grb_scc": [_vp, _vp, _vp, C.POINTER(SccResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

@@ -833,6 +833,25 @@ def kcore(v, A, k, desc):
     return info, _kcore_dict(res)
 
 
+def scc(v, A, desc):
+    """grb_scc: v = the strongly connected components of A's directed graph.  A is n x n, f32 or i32; its values are never
+    read (stored zeros are edges) and its diagonal takes no part.  x and y are in one component when a directed path runs
+    from x to y and one from y to x; v[x] = the smallest vertex number in x's component, so the same inputs give the same
+    bits and A and its transpose give the same vector.  On a symmetric structure these are the connected components.  v is
+    an i32 vector of size n and becomes dense; no descriptor field is read.  The whole computation (trimming, one
+    forward-backward sweep from a pivot, colouring rounds) is one launch on the device.  The CSR and the CSC are both read:
+    an A without a CSC of its own (a product result, the CSR-only format) -> GrB_INVALID_OBJECT.  A null or unbuilt
+    argument -> GrB_UNINITIALIZED_OBJECT; A not square or v not of size n -> GrB_DIMENSION_MISMATCH; v not i32 or A outside
+    f32 / i32 -> GrB_NOT_IMPLEMENTED; no device memory -> GrB_OUT_OF_MEMORY; a grid barrier that gave up -> GrB_PANIC (v
+    unchanged on every error).  Returns (info, dict(edges = stored off-diagonal entries, components, largest = vertices of
+    the largest component, trivial = components of one vertex, trimmed, rounds, passes = what the device ran, for the
+    bench only, launches, loop_ms))."""
+    res = _lib.SccResult()
+    info = _lib.load().grb_scc(_h(v), _h(A), _h(desc), C.byref(res))
+    return info, dict(edges=res.edges, components=res.components, largest=res.largest, trivial=res.trivial,
+                      trimmed=res.trimmed, rounds=res.rounds, passes=res.passes, launches=res.launches, loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

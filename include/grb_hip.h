@@ -1084,6 +1084,73 @@ typedef struct {
 grb_info grb_coreness(grb_vector core, grb_matrix A, grb_descriptor desc, grb_kcore_result* result);
 grb_info grb_kcore(grb_vector v, grb_matrix A, int k, grb_descriptor desc, grb_kcore_result* result);
 
+/* The strongly connected components (csrc/scc.hip): grb_scc.  The reference has no such driver (graphblas/algorithm/), so
+ * the definition is this header's own; it is the textbook's, and the directed counterpart of grb_cc.
+ *
+ * A is n x n, f32 or i32.  Stored values are never read: a stored zero is an edge.  Diagonal entries take no part.
+ *   E      = { (i, j) : A(i, j) stored, i != j }: the directed graph
+ *   u ~ v  when a directed path runs from u to v and one from v to u, or u = v.  The classes of ~ are the strongly connected
+ *            components
+ *   scc(v) = the smallest vertex number in v's component.
+ * That label is unique, so the same inputs give the same bits whatever order the device works in, and A and its transpose
+ * give the same vector.
+ *
+ * grb_scc(scc, A, desc, result): scc is an i32 vector of size n; it becomes dense with all n values stored.  desc may be
+ * NULL; no descriptor field is read: the components of the transpose are those of A.  result may be NULL.  On a symmetric
+ * structure the result is the connected components, labelled by their smallest member.
+ *
+ * Structure (the rule of grb_lcc and grb_cdlp with directed = 1): the CSR (out-edges) and the CSC (in-edges) are both read.
+ * An A without a CSC of its own (a product result, the CSR-only matrix format) is GRB_INVALID_OBJECT.
+ *
+ * How: the whole computation is ONE co-resident launch of a 1024-thread workgroup per CU (GRB_NUM_CU is honoured) whose
+ * passes are separated by a grid barrier with bounded spins; the host reads one record at the end, so launches is 1 whatever
+ * the graph.  Everything works on the live vertices, those without a label yet, in three phases.
+ *   1. Trim.  A live vertex with no live in-neighbour or no live out-neighbour is a component of its own.  The live in- and
+ *      out-degrees start as column and row length minus a stored diagonal.  ONE queue holds every vertex in the order of
+ *      its removal; the frontier of a pass is what the pass before appended.  Removing v gives every live out-neighbour one
+ *      returning integer atomic decrement of its in-degree and every live in-neighbour one of its out-degree; the thread
+ *      that sees a degree reach 0 claims the vertex with one atomic on its state word, so it is appended exactly once though
+ *      both degrees may get there.  Trimming runs to its fixpoint; it alone finishes every acyclic graph.
+ *   2. The giant component.  The pivot is the live vertex with the largest live in-degree x live out-degree (64 bits), the
+ *      smallest number on a tie.  A forward sweep over rows marks what it reaches; a backward sweep over columns that stays
+ *      inside the marked set removes what it reaches: the pivot's component.  Its smallest number is taken with a wave
+ *      reduction and one atomic per wave and written as the label.  Both sweeps are level-synchronous plain pushes over a
+ *      queue.  Trimming runs again.
+ *   3. Colouring rounds until no vertex is live.  colour(v) = v on the live vertices; the minimum travels along live edges
+ *      to a fixpoint (a vertex whose colour dropped is queued, once per pass, by a bit of its state word; its neighbours
+ *      get atomicMin).  The live vertices with colour(r) = r are the roots, each the smallest member of its own component,
+ *      so the label needs no reduction.  From all roots at once a sweep against the direction that stays inside the colour
+ *      removes every root's component, and trimming runs again.  Even rounds colour along rows and collect along columns,
+ *      odd rounds the other way round, so that a one-way chain of small components costs a single round one way or the
+ *      other.  The smallest live vertex is always a root, so every round removes a component and n rounds bound the loop;
+ *      the worst case stays quadratic in passes on adversarial inputs.
+ * Rows and columns are walked by a lane up to 8 entries, a wave with 16-byte index loads up to 2048, the workgroup beyond.
+ * Appends are staged per wave in LDS and reserved with one atomic per batch.  Working memory: 24 bytes per vertex (state
+ * word, two degrees, colour, the queue and one more frontier) and 2 KiB, one allocation made before the kernel and freed
+ * before the call returns; nothing is allocated inside the loop and nothing is proportional to nvals.
+ *
+ * edges, components, largest and trivial are exact and do not depend on scheduling; trimmed, rounds and passes may, and
+ * are for the bench only.
+ *
+ * Every error is found before scc is written, and scc keeps what it held: values, sparsity and caller-owned storage alike.
+ * A null scc or A, or an unbuilt A: GRB_UNINITIALIZED_OBJECT; A not square, or size(scc) != n: GRB_DIMENSION_MISMATCH; scc
+ * not i32, or A outside f32 / i32: GRB_NOT_IMPLEMENTED; an A without a CSC of its own: GRB_INVALID_OBJECT; a failed device
+ * allocation: GRB_OUT_OF_MEMORY; a grid barrier that gave up: GRB_PANIC, as in the other one-launch drivers.  n = 0 is a
+ * success with a zero record.  An A without off-diagonal entries is a success with scc(v) = v, components = trivial = n,
+ * and largest = 1 when n > 0. */
+typedef struct {
+  int64_t edges;        /* |E|: stored off-diagonal entries                                                   */
+  int32_t components;   /* number of components; n for an acyclic graph                                       */
+  int32_t largest;      /* vertices of the largest component; 0 when n = 0                                    */
+  int32_t trivial;      /* components of exactly one vertex                                                   */
+  int32_t trimmed;      /* vertices settled by trimming: implementation-defined, for the bench only           */
+  int32_t rounds;       /* colouring rounds (above): implementation-defined, for the bench only               */
+  int32_t passes;       /* grid-wide passes the device ran: implementation-defined, for the bench only        */
+  int32_t launches;     /* kernel launches of the loop itself: 1                                              */
+  float   loop_ms;      /* HIP-event time of the call's device work                                           */
+} grb_scc_result;        /* 40 bytes */
+grb_info grb_scc(grb_vector scc, grb_matrix A, grb_descriptor desc, grb_scc_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
