@@ -852,6 +852,29 @@ def scc(v, A, desc):
                       trimmed=res.trimmed, rounds=res.rounds, passes=res.passes, launches=res.launches, loop_ms=res.loop_ms)
 
 
+def msf(Cm, comp, A, desc):
+    """grb_msf: Cm = the minimum spanning forest of A's weighted undirected graph.  A is n x n, f32 or i32, symmetric in
+    structure and in values; its diagonal takes no part, a stored zero is an edge of weight 0 and the weights ARE read.
+    The edges are totally ordered by the key (w, min(u, v), max(u, v)), compared lexicographically -- i32 weights as signed
+    integers, f32 weights by value with -0.0 and +0.0 the same weight and +-inf allowed -- and the forest is the one Kruskal
+    builds when it takes the edges in key order, so it is unique and the same inputs give the same bits.  Cm is n x n of A's
+    type and receives both directions of every forest edge with A's bits for it (columns ascending, empty rows for isolated
+    vertices, CSC = a copy of the CSR unless Cm is CSR only); Cm may be A.  comp is None or an i32 vector of size n that
+    becomes dense: comp[v] = the smallest vertex number in v's connected component.  No descriptor field is read.  The whole
+    loop (Boruvka rounds) is one launch on the device.  Only the CSR is read: with a CSC of its own an A whose structure or
+    values are not symmetric -> GrB_INVALID_VALUE, without one (a product result, the CSR-only format) the caller vouches for
+    it and the call stays bounded.  A NaN off the diagonal -> GrB_INVALID_VALUE.  A null or unbuilt argument ->
+    GrB_UNINITIALIZED_OBJECT; A not square, Cm not n x n or comp not of size n -> GrB_DIMENSION_MISMATCH; A outside f32 / i32 or
+    comp not i32 -> GrB_NOT_IMPLEMENTED; Cm not of A's type -> GrB_DOMAIN_MISMATCH; no device memory -> GrB_OUT_OF_MEMORY; a
+    grid barrier that gave up -> GrB_PANIC (Cm and comp unchanged on every error).  Returns (info, dict(edges, forest_edges =
+    n - components, weight = the forest's weights summed in f64 in a fixed order (i32: the exact integer sum), components,
+    isolated, rounds, passes = what the device ran, for the bench only, launches, loop_ms))."""
+    res = _lib.MsfResult()
+    info = _lib.load().grb_msf(_h(Cm), _h(comp), _h(A), _h(desc), C.byref(res))
+    return info, dict(edges=res.edges, forest_edges=res.forest_edges, weight=res.weight, components=res.components,
+                      isolated=res.isolated, rounds=res.rounds, passes=res.passes, launches=res.launches, loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

@@ -1151,6 +1151,87 @@ typedef struct {
 } grb_scc_result;        /* 40 bytes */
 grb_info grb_scc(grb_vector scc, grb_matrix A, grb_descriptor desc, grb_scc_result* result);
 
+/* The minimum spanning forest (csrc/msf.hip): grb_msf.  The reference has no such driver (graphblas/algorithm/), so the
+ * definition is this header's own; LAGraph ships the algorithm as LAGraph_msf.  It is the one driver beside SSSP that reads
+ * the stored values.
+ *
+ * A is n x n, f32 or i32, symmetric in structure and in values: A(i, j) and A(j, i) are both stored and equal.  Diagonal
+ * entries take no part.  A stored zero is an edge of weight 0.  The weights ARE read.
+ *   G     = the simple undirected weighted graph of A's off-diagonal entries
+ *   key   = (w, min(u, v), max(u, v)) of the edge {u, v} of weight w, compared lexicographically: a total order of the edges.
+ *           For i32, w is compared as a signed integer.  For f32, w is compared by value: -0.0 and +0.0 are the same weight,
+ *           +-inf are allowed, and a NaN anywhere off the diagonal is GRB_INVALID_VALUE
+ *   MSF   = the minimum spanning forest under that total order.  It is unique: it is the forest Kruskal builds when it takes
+ *           the edges in key order.
+ * It depends on no scheduling: the same inputs give the same bits.  A relabelled graph gives the relabelled forest only up to
+ * the tie-break (the key holds vertex numbers), so nothing more may be expected on ties.
+ *
+ * grb_msf(C, comp, A, desc, result):
+ *   C      n x n and of A's element type; any other type is GRB_DOMAIN_MISMATCH.  C receives both directions of every forest
+ *          edge with its weight: columns ascending, empty rows for isolated vertices.  The CSC is a copy of the CSR, unless C
+ *          is in the CSR-only format.  C may be A.  The stored weight is A's bits for that entry; a -0.0 stays -0.0, taken
+ *          from the row of min(u, v).
+ *   comp   may be NULL.  Otherwise an i32 vector of size n that becomes dense: comp(v) = the smallest vertex number in v's
+ *          connected component, which is what grb_scc returns on a symmetric structure.
+ *   desc   may be NULL; no descriptor field is read.  result may be NULL.
+ * weight: for i32 the exact 64-bit integer sum, converted once to double.  For f32 an f64 sum taken in a fixed order over C's
+ * stored entries above the diagonal (each edge once): blocks of partial sums whose shape depends only on n and forest_edges,
+ * no floating-point atomics, so the bits repeat.
+ *
+ * Structure (the rule of grb_kcore): only the CSR is read.  When A has a CSC of its own, one comparison on the device before
+ * the loop checks the CSR against the CSC: pointers, indices and also values, compared as bits after -0 has been mapped to
+ * +0 (f32); a mismatch is GRB_INVALID_VALUE.  An A without a CSC of its own (a product result, the CSR-only matrix format) is
+ * taken on the caller's word: whatever it holds, nothing is read or written out of bounds and the call returns -- the rounds
+ * are bounded by 32, every pointer-jumping loop is bounded and forest appends are clamped to n - 1 -- and the output is then
+ * unspecified.  The NaN scan runs in both cases: the first round reads every off-diagonal value.
+ *
+ * How: Boruvka, as ONE co-resident launch of a 1024-thread workgroup per CU (GRB_NUM_CU is honoured) whose passes are
+ * separated by a grid barrier with bounded spins; the host reads one record at the end, so launches is 1 whatever the graph.
+ * State per vertex: the representative of its component, a parent word, a 64-bit best key and a 32-bit second word per
+ * component, the position of the vertex's candidate (or "finished"), and the forest list of (vertex, CSR position).  A round:
+ *   A. Every unfinished vertex walks its row (a lane for rows of up to 8 entries, a wave with 16-byte index loads up to 2048,
+ *      the workgroup beyond) and keeps the smallest key among the entries whose other end lies in another component; for a
+ *      fixed vertex the key order is the order of (w, other end), one 64-bit compare.  A vertex all of whose neighbours share
+ *      its component is finished and never walked again: components only merge.  The candidate gets one 64-bit atomicMin of
+ *      (ordered weight bits << 32 | min endpoint) at its component's slot; the ordered bits are the usual monotone map for
+ *      f32 with -0 canonicalised, a sign flip for i32.
+ *   B. The vertices whose candidate equals the slot take a 32-bit atomicMin of the max endpoint.
+ *   C. Exactly one vertex per component matches all three, and it owns the component's edge.  Ties are never broken by CSR
+ *      position: the two directions of an edge sit at different positions.  Under a total order the only hook cycles are
+ *      mutual pairs, two components that chose the same edge: the smaller representative stays root and alone appends the
+ *      edge; otherwise the hooking component appends it.  Appends are staged per wave in LDS and reserved with one atomic per
+ *      batch.
+ *   D. Pointer jumping to the fixpoint: up to 16 parents a vertex and pass, at most 40 passes.
+ *   E. comp(v) = parent(comp(v)); the slots are reset.
+ * The loop stops when no vertex has a candidate or a round hooks nothing.  Then comp(v) becomes the smallest member (one
+ * atomicMin per vertex at its root and a relabelling pass).  After the loop the forest list is expanded to both directions
+ * and ordered by the library's radix sort on (row, column) -- a star's forest row is as long as the star, so rows are not
+ * sorted one by one -- the pointers are a lower bound per row, and the weight is summed as above.  Working memory: 56 bytes
+ * per vertex and 4.3 KiB, one allocation made before the kernel and freed before the call returns; nothing is allocated
+ * inside the loop and nothing is proportional to nvals.  The sort after the loop brings 24 bytes per vertex of its own.
+ *
+ * edges, forest_edges, weight, components and isolated are exact and do not depend on scheduling; rounds and passes are for
+ * the bench only.
+ *
+ * Every error is found before C or comp is written, and both keep what they held.  A null C or A, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, C not n x n, or size(comp) != n: GRB_DIMENSION_MISMATCH; A outside f32 / i32, or comp
+ * not i32: GRB_NOT_IMPLEMENTED; C not of A's type: GRB_DOMAIN_MISMATCH; an asymmetric A (structure or values), or a NaN off the
+ * diagonal: GRB_INVALID_VALUE; a failed device allocation: GRB_OUT_OF_MEMORY; a grid barrier that gave up: GRB_PANIC, as in the
+ * other one-launch drivers.  n = 0 is a success with a zero record.  An A without off-diagonal entries is a success with an
+ * empty C, comp(v) = v, components = isolated = n and weight 0. */
+typedef struct {
+  int64_t edges;         /* undirected edges of G                                                    */
+  int64_t forest_edges;  /* edges of the forest = n - components                                     */
+  double  weight;        /* sum of the forest's weights                                              */
+  int32_t components;    /* connected components of G, isolated vertices included                    */
+  int32_t isolated;      /* vertices without an off-diagonal entry                                   */
+  int32_t rounds;        /* Boruvka rounds: implementation-defined, for the bench only               */
+  int32_t passes;        /* grid-wide passes the device ran: implementation-defined, bench only      */
+  int32_t launches;      /* kernel launches of the loop itself: 1                                    */
+  float   loop_ms;       /* HIP-event time of the call's device work                                 */
+} grb_msf_result;         /* 48 bytes */
+grb_info grb_msf(grb_matrix C, grb_vector comp, grb_matrix A, grb_descriptor desc, grb_msf_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
