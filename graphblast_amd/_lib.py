@@ -70,6 +70,12 @@ class MsfResult(C.Structure):
                 ("loop_ms", C.c_float)]
 
 
+class MatchingResult(C.Structure):
+    _fields_ = [("edges", C.c_int64), ("matched", C.c_int64), ("weight", C.c_double), ("exposed", C.c_int32),
+                ("isolated", C.c_int32), ("rounds", C.c_int32), ("passes", C.c_int32), ("evaluations", C.c_int32),
+                ("launches", C.c_int32), ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -239,6 +245,7 @@ _SIGS = {
     "grb_kcore": [_vp, _vp, _i, _vp, C.POINTER(KcoreResult)],
     "grb_scc": [_vp, _vp, _vp, C.POINTER(SccResult)],
     "grb_msf": [_vp, _vp, _vp, _vp, C.POINTER(MsfResult)],
+    "grb_matching": [_vp, _vp, _vp, _i, C.c_uint32, _vp, C.POINTER(MatchingResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

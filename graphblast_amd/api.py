@@ -875,6 +875,38 @@ def msf(Cm, comp, A, desc):
                       isolated=res.isolated, rounds=res.rounds, passes=res.passes, launches=res.launches, loop_ms=res.loop_ms)
 
 
+GRB_MATCH_HEAVIEST, GRB_MATCH_LIGHTEST, GRB_MATCH_HASHED = 0, 1, 2
+
+
+def matching(mate, Cm, A, mode, seed, desc):
+    """grb_matching: mate = the greedy matching of A's undirected graph.  A is n x n, f32 or i32, symmetric; its diagonal
+    takes no part.  The edges are totally ordered by the key (p, min(u, v), max(u, v)), compared lexicographically, and the
+    matching is the one the greedy scan builds: take the edges in key order and keep an edge when both ends are still free.
+    It is unique and maximal, so the same inputs give the same bits.  mode selects p: GRB_MATCH_HEAVIEST = 0 orders by
+    descending weight (i32 as signed integers; f32 by value with -0.0 and +0.0 the same weight and +-inf allowed; a stored
+    zero or a negative weight is an edge like any other; its weight is at least half the maximum weight matching's when the
+    weights are non-negative), GRB_MATCH_LIGHTEST = 1 the same ascending, GRB_MATCH_HASHED = 2 reads the structure only:
+    p = mix(mix(min + seed) ^ max) in 32-bit unsigned arithmetic with mix(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13;
+    x *= 0xc2b2ae35; x ^= x >> 16, the smaller p first; seed is ignored in the other modes.  mate is an i32 vector of size n
+    that becomes dense: mate[v] = v's partner, or -1.  Cm is None or n x n of A's type and receives both directions of every
+    matched edge, at most one entry a row, with A's bits from the row of min(u, v) (CSC = a copy of the CSR unless Cm is CSR
+    only); Cm may be A.  No descriptor field is read.  The whole loop (locally dominant edges) is one launch on the device.
+    Only the CSR is read: with a CSC of its own an A whose structure (in modes 0 and 1: or values) is not symmetric ->
+    GrB_INVALID_VALUE, without one (a product result, the CSR-only format) the caller vouches for it and the call stays
+    bounded.  A NaN off the diagonal in modes 0 and 1, or a mode outside 0..2 -> GrB_INVALID_VALUE.  A null or unbuilt
+    argument -> GrB_UNINITIALIZED_OBJECT; A not square, mate not of size n or Cm not n x n -> GrB_DIMENSION_MISMATCH; A outside
+    f32 / i32 or mate not i32 -> GrB_NOT_IMPLEMENTED; Cm not of A's type -> GrB_DOMAIN_MISMATCH; no device memory ->
+    GrB_OUT_OF_MEMORY; a grid barrier that gave up -> GrB_PANIC (mate and Cm unchanged on every error).  Returns (info,
+    dict(edges, matched = the edges of the matching, weight = the matched edges' stored values summed in f64 in a fixed order
+    (i32: the exact integer sum), exposed = vertices with a neighbour but no partner, isolated, rounds, passes, evaluations =
+    what the device ran, for the bench only, launches, loop_ms))."""
+    res = _lib.MatchingResult()
+    info = _lib.load().grb_matching(_h(mate), _h(Cm), _h(A), int(mode), int(seed) & 0xffffffff, _h(desc), C.byref(res))
+    return info, dict(edges=res.edges, matched=res.matched, weight=res.weight, exposed=res.exposed, isolated=res.isolated,
+                      rounds=res.rounds, passes=res.passes, evaluations=res.evaluations, launches=res.launches,
+                      loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

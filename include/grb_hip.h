@@ -1232,6 +1232,91 @@ typedef struct {
 } grb_msf_result;         /* 48 bytes */
 grb_info grb_msf(grb_matrix C, grb_vector comp, grb_matrix A, grb_descriptor desc, grb_msf_result* result);
 
+/* Greedy weighted and maximal matching (csrc/matching.hip): grb_matching.  The reference has no such driver
+ * (graphblas/algorithm/), so the definition is this header's own; LAGraph ships the algorithm as LAGraph_MaximalMatching.
+ *
+ * A is n x n, f32 or i32, symmetric.  Diagonal entries take no part.  G is the simple undirected graph of the off-diagonal
+ * entries.  Every edge {u, v} has a key (p, min(u, v), max(u, v)), compared lexicographically: a total order of the edges.
+ * mode selects p:
+ *   GRB_MATCH_HEAVIEST = 0   p orders by descending weight, heaviest first.  i32 weights are compared as signed integers.  f32
+ *                            weights are compared by value: -0.0 and +0.0 are the same weight, +-inf are allowed, and a NaN
+ *                            off the diagonal is GRB_INVALID_VALUE.  A stored zero or a negative weight is an edge like any
+ *                            other.
+ *   GRB_MATCH_LIGHTEST = 1   the same, ascending.
+ *   GRB_MATCH_HASHED   = 2   structure only: the values are never compared, a NaN is fine.  p = mix(mix(min + seed) ^ max) in
+ *                            32-bit unsigned arithmetic, where mix(x) is x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13;
+ *                            x *= 0xc2b2ae35; x ^= x >> 16.  The smaller p goes first.  seed is ignored in the other modes.
+ * The matching M is the one the greedy scan builds: take the edges in key order and keep an edge when both ends are still
+ * free.  M is unique, and it is maximal: no edge of G has two free ends.  In mode 0 its weight is at least half the maximum
+ * weight matching's, when the weights are non-negative.  In mode 2 it is a maximal cardinality matching with random-looking
+ * priorities, reproducible from seed.  It depends on no scheduling: the same inputs give the same bits.
+ *
+ * grb_matching(mate, C, A, mode, seed, desc, result):
+ *   mate   an i32 vector of size n.  It becomes dense: mate(v) = v's partner, or -1.
+ *   C      may be NULL.  Otherwise n x n and of A's element type; any other type is GRB_DOMAIN_MISMATCH.  C receives both
+ *          directions of every matched edge, at most one entry a row.  Both directions hold A's bits from the row of
+ *          min(u, v), as in grb_msf.  The CSC is a copy of the CSR, unless C is in the CSR-only format.  C may be A.
+ *   desc   may be NULL; no descriptor field is read.  result may be NULL.
+ * weight follows grb_msf's rule: for i32 the exact 64-bit integer sum, converted once to double.  For f32 an f64 sum taken in
+ * a fixed order over the matched entries above the diagonal (each edge once): blocks of partial sums whose shape depends on
+ * n alone, no floating-point atomics, so the bits repeat.  In mode 2 it is the same sum of the stored values.
+ *
+ * Symmetry follows grb_msf's rule: only the CSR is read.  When A has a CSC of its own, one comparison on the device before
+ * the loop checks the CSR against the CSC: pointers and indices, and in modes 0 and 1 also values, compared as bits after -0
+ * has been mapped to +0 (f32); a mismatch is GRB_INVALID_VALUE.  An A without a CSC of its own (a product result, the
+ * CSR-only matrix format) is taken on the caller's word: whatever it holds, nothing is read or written out of bounds and the
+ * call returns -- a round that matches nothing is the last, so the rounds are bounded by n / 2 + 1, and the appends to the
+ * queue and to the list of the matched are clamped to n -- and the output is then unspecified.  The NaN scan of modes 0 and
+ * 1 runs in both cases: the first round reads every off-diagonal value.
+ *
+ * How: the locally dominant edge algorithm.  An edge that is the best live edge at both of its ends is in the greedy matching
+ * of what is left.  ONE co-resident launch of a 1024-thread workgroup per CU (GRB_NUM_CU is honoured) whose passes are
+ * separated by a grid barrier with bounded spins; the host reads one record at the end, so launches is 1 whatever the graph.
+ * State per vertex: mate, the other end and the CSR position of its best live entry (or "finished"), one queue of vertices to
+ * evaluate and one list of the matched.  A round:
+ *   A. Every queued vertex (in the first round: every vertex with a neighbour) walks its row (a lane for rows of up to 8
+ *      entries, a wave with 16-byte index loads up to 2048, the workgroup beyond) for the smallest 64-bit (ordered p << 32 |
+ *      other end) among the entries whose other end has no partner; for a fixed vertex that is the order of the key.  The
+ *      ordered bits are the usual monotone map for f32 with -0 canonicalised, a sign flip for i32, complemented in mode 0.
+ *      No atomic: the walker owns its candidate.  A vertex with no free neighbour is finished for good.
+ *   B. Every evaluated v with cand(cand(v)) = v is matched.  Either end or both may see the pair; each end is claimed by one
+ *      compare-and-swap of its mate, and the claimer appends it to the list, so a vertex enters the list exactly once.
+ *   C. Every newly matched x walks its row and queues each free neighbour y with cand(y) = x.  A vertex whose candidate is
+ *      still free keeps it and is not walked again: 1.3 to 1.7 evaluations a vertex measured on paths, grids and RMAT
+ *      graphs with random or hashed keys.
+ * Appends are staged per wave in LDS and reserved with one atomic per batch.  The loop stops when the queue is empty or a
+ * round matched nothing.  The worst case is equal weights, where the key falls back to vertex numbers: a path then takes
+ * n / 2 rounds of three barrier-bound passes.  After the loop C needs no sort: pointers = a scan of (mate >= 0), index =
+ * mate, value = the stored position's bits.  Working memory: 24 bytes per vertex and about 3 KiB, one allocation made before
+ * the kernel and freed before the call returns; nothing is allocated inside the loop and nothing is proportional to nvals.
+ *
+ * edges, matched, weight, exposed and isolated are exact and do not depend on scheduling; rounds, passes and evaluations are
+ * for the bench only.
+ *
+ * Every error is found before mate or C is written, and both keep what they held.  A null mate or A, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, size(mate) != n, or C not n x n: GRB_DIMENSION_MISMATCH; A outside f32 / i32, or mate
+ * not i32: GRB_NOT_IMPLEMENTED; C not of A's type: GRB_DOMAIN_MISMATCH; mode outside 0..2, an asymmetric A, or a NaN off the
+ * diagonal in modes 0 and 1: GRB_INVALID_VALUE; a failed device allocation: GRB_OUT_OF_MEMORY; a grid barrier that gave up:
+ * GRB_PANIC, as in the other one-launch drivers.  n = 0 is a success with a zero record.  An A without off-diagonal entries
+ * is a success with mate = -1 everywhere and an empty C. */
+#define GRB_MATCH_HEAVIEST 0
+#define GRB_MATCH_LIGHTEST 1
+#define GRB_MATCH_HASHED 2
+typedef struct {
+  int64_t edges;         /* undirected edges of G                                                    */
+  int64_t matched;       /* edges of M                                                               */
+  double  weight;        /* sum of the matched edges' stored values                                  */
+  int32_t exposed;       /* vertices with a neighbour but no partner                                 */
+  int32_t isolated;      /* vertices without an off-diagonal entry                                   */
+  int32_t rounds;        /* rounds of the loop: implementation-defined, for the bench only           */
+  int32_t passes;        /* grid-wide passes the device ran: implementation-defined, bench only      */
+  int32_t evaluations;   /* rows walked for a candidate: implementation-defined, bench only          */
+  int32_t launches;      /* kernel launches of the loop itself: 1                                    */
+  float   loop_ms;       /* HIP-event time of the call's device work                                 */
+} grb_matching_result;    /* 56 bytes */
+grb_info grb_matching(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uint32_t seed, grb_descriptor desc,
+                      grb_matching_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
