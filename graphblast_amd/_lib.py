@@ -76,6 +76,11 @@ class MatchingResult(C.Structure):
                 ("launches", C.c_int32), ("loop_ms", C.c_float)]
 
 
+class ContractResult(C.Structure):
+    _fields_ = [("kept", C.c_int64), ("loops", C.c_int64), ("entries", C.c_int64), ("clusters", C.c_int32),
+                ("dropped", C.c_int32), ("largest", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -246,6 +251,8 @@ _SIGS = {
     "grb_scc": [_vp, _vp, _vp, C.POINTER(SccResult)],
     "grb_msf": [_vp, _vp, _vp, _vp, C.POINTER(MsfResult)],
     "grb_matching": [_vp, _vp, _vp, _i, C.c_uint32, _vp, C.POINTER(MatchingResult)],
+    "grb_relabel": [_vp, _vp, _i, C.POINTER(C.c_int32), _vp],
+    "grb_contract": [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(ContractResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

@@ -907,6 +907,50 @@ def matching(mate, Cm, A, mode, seed, desc):
                       loop_ms=res.loop_ms)
 
 
+GRB_RELABEL_LABELS, GRB_RELABEL_MATE = 0, 1
+
+
+def relabel(map, labels, kind):
+    """grb_relabel: map = the dense ranking of a label vector.  labels is an i32 vector of size n in either storage with all
+    n values stored.  kind = GRB_RELABEL_LABELS (0): every value is in 0 .. n - 1 and L(v) = labels[v]; GRB_RELABEL_MATE (1):
+    every value is in -1 .. n - 1 and L(v) = v when labels[v] < 0, otherwise min(v, labels[v]) -- what grb_matching writes,
+    so a matched pair shares a label and an unmatched vertex keeps its own (the involution is not checked).  map is an i32
+    vector of size n that becomes dense: map[v] = the number of distinct values of L smaller than L(v), so the coarse ids
+    ascend with the labels; map may be labels.  Flags, the library's scan and a gather on the device; the same inputs give
+    the same bits.  Errors are found before map is written: a null handle -> GrB_UNINITIALIZED_OBJECT; sizes differ ->
+    GrB_DIMENSION_MISMATCH; not i32 -> GrB_NOT_IMPLEMENTED; nvals(labels) != n or kind outside {0, 1} -> GrB_INVALID_VALUE; a
+    value out of range -> GrB_INVALID_INDEX.  Returns (info, count = the number of distinct values of L; 0 when n = 0)."""
+    count = C.c_int32(0)
+    info = _lib.load().grb_relabel(_h(map), _h(labels), int(kind), C.byref(count), None)
+    return info, count.value
+
+
+def contract(Cm, sizes, A, map, op, loops, desc):
+    """grb_contract: Cm = S^T A S with S(v, map[v]) = 1, the quotient graph.  A is n x n, f32 or i32, any structure (only
+    its CSR is read; stored zeros are entries).  map is an i32 vector of size n with all n values stored, each in
+    -1 .. nc - 1 where Cm is nc x nc: -1 drops the vertex with every entry of its row and column, anything else out of range
+    -> GrB_INVALID_INDEX.  A raw label vector works with an n x n Cm (unused labels leave empty rows), a relabel() result with
+    an nc x nc Cm.  loops = 0 drops every entry with map[i] = map[j] (condensation, coarsening), 1 keeps them (community
+    graph).  Cm(a, b) is stored exactly when some stored A(i, j) has map[i] = a, map[j] = b and survives loops; columns
+    ascend; its value is the fold of the contributing entries under op, a binary operator by name or number: "plus" (i32
+    wraps; f32 adds in f64 in an order fixed by the inputs alone and rounds once, no floating-point atomics), "minimum" /
+    "maximum" (i32 signed; f32 in the total order -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN, the winner's bits
+    copied), "first" (the bits of the contributing entry with the smallest (i, j)); any other -> GrB_NOT_IMPLEMENTED.  Cm is
+    of A's type (else GrB_DOMAIN_MISMATCH) and gets its CSR and, unless it is CSR only, a CSC that is the transpose of that
+    CSR; Cm may be A when nc = n.  sizes is None or an i32 vector of size nc that becomes dense: sizes[a] = the vertices
+    mapped to a.  No descriptor field is read.  A null or unbuilt argument -> GrB_UNINITIALIZED_OBJECT; A or Cm not square,
+    map not of size n or sizes not of size nc -> GrB_DIMENSION_MISMATCH; A outside f32 / i32, map or sizes not i32 ->
+    GrB_NOT_IMPLEMENTED; loops outside {0, 1} or nvals(map) != n -> GrB_INVALID_VALUE; no device memory -> GrB_OUT_OF_MEMORY
+    (Cm and sizes unchanged on every error).  Returns (info, dict(kept = entries of A with both ends kept, loops = those with
+    map[i] = map[j] whatever the flag, entries = nvals(Cm), clusters = non-empty clusters, dropped = vertices with map -1,
+    largest = the largest cluster, launches, loop_ms))."""
+    res = _lib.ContractResult()
+    opn = op if isinstance(op, int) else BINARY_OPS.index(op)
+    info = _lib.load().grb_contract(_h(Cm), _h(sizes), _h(A), _h(map), int(opn), int(loops), _h(desc), C.byref(res))
+    return info, dict(kept=res.kept, loops=res.loops, entries=res.entries, clusters=res.clusters, dropped=res.dropped,
+                      largest=res.largest, launches=res.launches, loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

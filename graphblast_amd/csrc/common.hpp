@@ -891,6 +891,8 @@ struct Side {
 bool has_csc(const grb_matrix_s* X);
 // C is replaced by r (its CSR) and c (its CSC, nullable); an input that is C is read before this
 grb_info attach(grb_matrix C, Side* r, Side* c);
+// the transpose of an m x n CSR (the n rows of the result) by a sort on the device: what grb_transpose does without a CSC
+grb_info transpose_side(const CsrArrays& X, Index m, Index n, Side* out);
 // extract.hip: C = op(A)(I, J), w = op(A)(I, j), w = u(I) (grb_hip.h: the three extract forms); null lists: all, in order
 grb_info extract_matrix(grb_matrix C, grb_matrix A, const Index* rows, Index nrows, const Index* cols, Index ncols, bool tran);
 grb_info extract_matrix_col(grb_vector w, grb_matrix A, const Index* rows, Index nrows, Index col, bool tran);

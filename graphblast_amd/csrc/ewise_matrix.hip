@@ -520,6 +520,9 @@ grb_info sort_side(const CsrArrays& X, Index m, Index n, Side* out) {
 }
 }  // namespace
 
+// ... for a result that has only its CSR so far (contract.hip)
+grb_info transpose_side(const CsrArrays& X, Index m, Index n, Side* out) { return sort_side(X, m, n, out); }
+
 grb_info transpose_matrix(grb_matrix C, grb_matrix A, bool tran) {
   if ((A->dtype != GRB_F32 && A->dtype != GRB_I32) || C->dtype != A->dtype) return GRB_NOT_IMPLEMENTED;
   const Index m = tran ? A->nrows : A->ncols, n = tran ? A->ncols : A->nrows;   // C is m x n

@@ -1317,6 +1317,88 @@ typedef struct {
 grb_info grb_matching(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uint32_t seed, grb_descriptor desc,
                       grb_matching_result* result);
 
+/* Graph contraction (csrc/contract.hip): grb_relabel and grb_contract.  The reference has no such driver
+ * (graphblas/algorithm/), so the definitions are this header's own; LAGraph ships the operation as LAGraph_Coarsen_Matching,
+ * cuGraph as coarsen_graph, networkx as quotient_graph / condensation.  They consume what grb_cc, grb_scc, grb_msf (comp),
+ * grb_cdlp, grb_coreness and grb_matching produce: a partition of the vertices as a vector.
+ *
+ * grb_relabel(map, labels, kind, count, desc): the dense ranking of a label vector.
+ *   labels  an i32 vector of size n, in either storage, with all n values stored (grb_cdlp's rule for init).
+ *   kind    GRB_RELABEL_LABELS = 0   every value is in 0 .. n - 1, and L(v) = labels(v).
+ *           GRB_RELABEL_MATE   = 1   every value is in -1 .. n - 1, and L(v) = v when labels(v) < 0, otherwise
+ *                                    min(v, labels(v)): what grb_matching writes, so a matched pair shares a label and an
+ *                                    unmatched vertex keeps its own.  The involution is not checked; the rule is applied as
+ *                                    written.
+ *   map     an i32 vector of size n.  It becomes dense: map(v) = the number of distinct values of L smaller than L(v), so the
+ *           coarse ids ascend with the labels.  map may be labels.
+ *   count   nullable: the number of distinct values of L, nc.      desc may be NULL; no field is read.
+ * How: one word per possible label set where the label is in use, the library's exclusive scan, a gather.  The host reads nc
+ * and the range check's flag in one wait.  The same inputs give the same bits.
+ * Errors are found before map is written.  A null handle: GRB_UNINITIALIZED_OBJECT; sizes differ: GRB_DIMENSION_MISMATCH; not
+ * i32: GRB_NOT_IMPLEMENTED; nvals(labels) != n, or kind outside {0, 1}: GRB_INVALID_VALUE; a value out of range, found by one
+ * reduction on the device: GRB_INVALID_INDEX; a failed device allocation: GRB_OUT_OF_MEMORY.  n = 0: success, count 0.
+ *
+ * grb_contract(C, sizes, A, map, op, loops, desc, result): the quotient graph C = S^T A S with S(v, map(v)) = 1.
+ *   A       n x n, f32 or i32, any structure (directed is fine).  Only the CSR is read, so a product result and the CSR-only
+ *           matrix format work.  Stored zeros are entries.
+ *   map     an i32 vector of size n with all n values stored, each in -1 .. nc - 1, where nc is C's own shape: C is nc x nc.
+ *           map(v) = -1 drops vertex v with every entry of its row and column.  Anything else out of range is
+ *           GRB_INVALID_INDEX, checked on the device before anything is written.  A raw label vector therefore works with an
+ *           n x n C (the rows of unused labels stay empty), a grb_relabel result with an nc x nc C.
+ *   loops   0 drops every entry with map(i) = map(j) (the condensation, a coarsening step); 1 keeps them (the community
+ *           graph).
+ *   C       of A's type, else GRB_DOMAIN_MISMATCH.  C(a, b) is stored exactly when some stored A(i, j) has map(i) = a and
+ *           map(j) = b and survives loops.  Columns ascend in every row.  C gets its CSR, and a CSC made by transposing that
+ *           CSR on the device (the path behind grb_transpose): the same entries and bits, never a second fold.  A C of the
+ *           CSR-only format aliases its CSC as in every other operation.  C may be A when nc = n.
+ *   op      how the contributions to one C(a, b) are combined, a grb_binary_op; any but these four is GRB_NOT_IMPLEMENTED:
+ *           GRB_OP_PLUS      i32: two's-complement wrap-around.  f32: an f64 sum rounded to f32 once, taken in an order that
+ *                            is a function of the inputs alone, not of GRB_NUM_CU or of scheduling: up to 32 contributions in
+ *                            the order of (i, j); more, in pieces of 2048 consecutive contributions, inside a piece 64
+ *                            interleaved partial sums joined by a fixed butterfly, the pieces' sums joined the same way.  No
+ *                            floating-point atomic, so the bits repeat.
+ *           GRB_OP_MINIMUM / GRB_OP_MAXIMUM   i32 as signed integers; f32 in the total order of the usual monotone map of the
+ *                            bits: -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN.  The winner's bits are copied, so no
+ *                            order of evaluation can show.
+ *           GRB_OP_FIRST     the bits of the contributing entry with the smallest (i, j).
+ *   sizes   nullable: an i32 vector of size nc.  It becomes dense: sizes(a) = |{v : map(v) = a}|.
+ *   desc    may be NULL; no descriptor field is read.  result may be NULL.
+ * How: one sort-based path for every operator and every coarse row, in a fixed number of plain launches -- no level loop, no
+ * grid barrier.  Every stored entry gets the key (map(i) << cb | map(j)), cb = the bits of nc, and its CSR position as
+ * payload; an entry that does not survive gets a key above all others.  The library's stable radix sort over the 2 cb bits
+ * that matter brings the contributions of one (a, b) together, still in the order of (i, j).  Head flags and the library's scan
+ * number the runs; their total is nvals(C).  C's row pointers are a search per coarse row, the fold is a lane per run, and a
+ * run of more than 32 contributions is cut into pieces of 2048 folded by a wave each, so that "everything collapses into one
+ * entry" is 8192 pieces for sixteen million contributions and not a serial chain.  The host waits twice: for the range check
+ * with the counts, and for nvals(C).  Every index read from map or from A is checked against its array before it is used, so
+ * nothing is read or written out of bounds whatever map holds.  Working memory: about 24 bytes per stored entry of A in one
+ * allocation made up front, beside the sort's own 12 bytes per entry and the transposition's.
+ *
+ * kept, loops, entries, clusters, dropped and largest are exact and do not depend on scheduling; launches and loop_ms are for
+ * the bench only.
+ *
+ * Every error is found before C or sizes is written, and both keep what they held.  A null C, A or map, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, C not square, size(map) != n, or size(sizes) != nc: GRB_DIMENSION_MISMATCH; A outside
+ * f32 / i32, or map / sizes not i32: GRB_NOT_IMPLEMENTED; C not of A's type: GRB_DOMAIN_MISMATCH; an operator outside the four:
+ * GRB_NOT_IMPLEMENTED; loops outside {0, 1}, or nvals(map) != n: GRB_INVALID_VALUE; a map value out of range:
+ * GRB_INVALID_INDEX; a failed device allocation: GRB_OUT_OF_MEMORY.  n = 0, nc = 0 or an A without entries: success with an
+ * empty C. */
+#define GRB_RELABEL_LABELS 0
+#define GRB_RELABEL_MATE 1
+typedef struct {
+  int64_t kept;          /* entries of A with both ends kept                                         */
+  int64_t loops;         /* those with map(i) = map(j), before combining, whatever the flag          */
+  int64_t entries;       /* nvals(C)                                                                 */
+  int32_t clusters;      /* non-empty clusters                                                       */
+  int32_t dropped;       /* vertices with map -1                                                     */
+  int32_t largest;       /* the largest cluster                                                      */
+  int32_t launches;      /* kernel launches of the call: implementation-defined, bench only          */
+  float   loop_ms;       /* HIP-event time of the call's device work                                 */
+} grb_contract_result;    /* 48 bytes */
+grb_info grb_relabel(grb_vector map, grb_vector labels, int kind, int32_t* count, grb_descriptor desc);
+grb_info grb_contract(grb_matrix C, grb_vector sizes, grb_matrix A, grb_vector map, grb_binary_op op, int loops,
+                      grb_descriptor desc, grb_contract_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
