@@ -951,6 +951,39 @@ def contract(Cm, sizes, A, map, op, loops, desc):
                       largest=res.largest, launches=res.launches, loop_ms=res.loop_ms)
 
 
+GRB_FLOW_CAPACITY, GRB_FLOW_UNIT = 0, 1
+
+
+def maxflow(F, side, A, source, sink, mode, desc):
+    """grb_maxflow: the maximum flow from source to sink and its minimum cut.  A is n x n, f32 or i32, directed: A(i, j) is
+    the capacity of the arc i -> j; no symmetry is asked for, diagonal entries take no part, antiparallel arcs are two arcs
+    and a stored 0 is an arc of capacity 0.  mode = GRB_FLOW_CAPACITY = 0 reads the values: i32 must be >= 0, f32 an integer
+    value in 0 .. 2^24 (anything else off the diagonal -- negative, fractional, NaN, +-inf, above 2^24 -> GrB_INVALID_VALUE);
+    GRB_FLOW_UNIT = 1 gives every stored off-diagonal entry capacity 1 and never reads the values (a NaN is fine).  The
+    arithmetic is exact: 32-bit residual capacities, 64-bit integer excesses and value, no floating-point atomics.  side is
+    None or an i32 vector of size n that becomes dense: side[v] = 1 when sink can be reached from v in the residual graph of a
+    maximum flow -- the smallest sink side of any minimum cut, unique; side[sink] = 1, side[source] = 0, and the arcs from
+    side 0 to side 1 are a minimum cut whose capacities sum to value.  F is None or n x n of A's type and receives a maximum
+    flow in cancelled form: entries only where A has one off the diagonal and the flow is positive, 0 < F(i, j) <= capacity,
+    never both F(i, j) and F(j, i), columns ascending, the CSC by transposition unless F is CSR only; F may be A.  F is a valid
+    maximum flow (capacity, conservation at every vertex but the terminals) and the same inputs give the same bits; with F
+    None the preflow is not converted to a flow.  No descriptor field is read.  Synchronous push-relabel with global
+    relabeling as one launch on the device; A's CSC is read for the reverse arcs.  A null or unbuilt A ->
+    GrB_UNINITIALIZED_OBJECT; A not square, F not n x n or side not of size n -> GrB_DIMENSION_MISMATCH; source or sink outside
+    0 .. n - 1 -> GrB_INDEX_OUT_OF_BOUNDS; source == sink, a mode outside 0..1 or a bad capacity -> GrB_INVALID_VALUE; A outside
+    f32 / i32 or side not i32 -> GrB_NOT_IMPLEMENTED; F not of A's type -> GrB_DOMAIN_MISMATCH; an A without a CSC of its own ->
+    GrB_INVALID_OBJECT; too many residual arcs or no device memory -> GrB_OUT_OF_MEMORY; a grid barrier that gave up ->
+    GrB_PANIC (F and side unchanged on every error).  Returns (info, dict(value, arcs = stored off-diagonal entries of A,
+    flow_arcs = nvals(F) or -1, sink_side = vertices with side 1, cut_arcs, cut_capacity = the cut's capacities summed after
+    the loop, always equal to value, rounds, global_relabels, passes = what the device ran, for the bench only, launches,
+    loop_ms))."""
+    res = _lib.MaxflowResult()
+    info = _lib.load().grb_maxflow(_h(F), _h(side), _h(A), int(source), int(sink), int(mode), _h(desc), C.byref(res))
+    return info, dict(value=res.value, arcs=res.arcs, flow_arcs=res.flow_arcs, sink_side=res.sink_side, cut_arcs=res.cut_arcs,
+                      cut_capacity=res.cut_capacity, rounds=res.rounds, global_relabels=res.global_relabels, passes=res.passes,
+                      launches=res.launches, loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

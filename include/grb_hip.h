@@ -1399,6 +1399,102 @@ grb_info grb_relabel(grb_vector map, grb_vector labels, int kind, int32_t* count
 grb_info grb_contract(grb_matrix C, grb_vector sizes, grb_matrix A, grb_vector map, grb_binary_op op, int loops,
                       grb_descriptor desc, grb_contract_result* result);
 
+/* Maximum flow and minimum cut (csrc/maxflow.hip): grb_maxflow.  The reference has no such driver (graphblas/algorithm/), so
+ * the definition is this header's own; LAGraph ships the algorithm as LAGr_MaxFlow.
+ *
+ * The network.  A is n x n, f32 or i32, directed: A(i, j) is the capacity of the arc i -> j.  No symmetry is asked for.
+ * Diagonal entries take no part.  Antiparallel arcs (both (i, j) and (j, i) stored) are two arcs.  A stored 0 is an arc of
+ * capacity 0.  mode selects how the values are read:
+ *   GRB_FLOW_CAPACITY = 0   the values are the capacities.  i32 must be >= 0.  f32 must be an integer value in 0 .. 2^24, so
+ *                           that it converts exactly.  Anything else off the diagonal (negative, fractional, NaN, +-inf,
+ *                           above 2^24) is GRB_INVALID_VALUE.
+ *   GRB_FLOW_UNIT     = 1   every stored off-diagonal entry has capacity 1 and the values are never read.  A NaN is fine.
+ * The arithmetic is exact: 32-bit residual capacities, 64-bit integer excesses and value (the value may exceed 2^32), and no
+ * floating-point atomic anywhere.  Integer atomic adds commute, which is what makes the bits repeat.
+ *
+ * grb_maxflow(F, side, A, source, sink, mode, desc, result):
+ *   result->value   the maximum flow value from source to sink.  It is unique.
+ *   side   may be NULL.  Otherwise an i32 vector of size n that becomes dense: side(v) = 1 when sink can be reached from v in
+ *          the residual graph of a maximum flow, 0 otherwise.  That set is the smallest sink side of any minimum cut.  It is
+ *          the same for every maximum flow and for every maximum preflow, so it is unique and needs no second phase.
+ *          side(sink) = 1, side(source) = 0.  The arcs from side 0 to side 1 are a minimum cut, and their capacities sum to
+ *          value.
+ *   F      may be NULL.  Otherwise n x n and of A's element type; any other type is GRB_DOMAIN_MISMATCH.  F receives a maximum
+ *          flow in cancelled form: there is an entry (i, j) only where A has one off the diagonal and the flow on it is
+ *          positive, 0 < F(i, j) <= capacity, and never both F(i, j) and F(j, i).  Columns ascending, both orientations built
+ *          (the CSC by the transposition behind grb_transpose, or aliased for a CSR-only F).  F may be A.  A maximum flow is
+ *          not unique as a mathematical object.  What is promised of F: it is a valid maximum flow (capacity, conservation at
+ *          every vertex but the two terminals, net outflow of source = net inflow of sink = value), and the same inputs give
+ *          the same bits on any number of CUs, like every other driver here.  When F is NULL the preflow is not converted to
+ *          a flow.
+ *   desc   may be NULL; no descriptor field is read.  result may be NULL.
+ *
+ * How: synchronous push-relabel with exact global relabeling.
+ *   1. Plain launches build the residual structure: the union of the off-diagonal structures of A and its transpose, rows in
+ *      CSR order (A's CSC is read for the reverse arcs, which is why A needs one of its own, as in grb_scc).  Per residual arc:
+ *      the other end, the residual capacity (A's capacity, or 0 for a pure reverse arc), the position of the twin arc, and
+ *      the position in A or -1.  Every row starts at a multiple of 16 bytes and is filled up to one.
+ *   2. ONE co-resident launch of a 1024-thread workgroup per CU (GRB_NUM_CU is honoured) whose passes are separated by a grid
+ *      barrier with bounded spins, so launches is 1 whatever the network.  The source's arcs are saturated.  A round:
+ *      push     every queued vertex u (excess > 0, not a terminal) walks its row in stored order against the heights and its
+ *               excess as they stood at the start of the round, and pushes min(remaining excess, residual) over every arc
+ *               with h(u) = h(v) + 1.  Under one snapshot of the heights only one direction of an arc pair can be
+ *               admissible, so the pusher alone writes the arc's residual and its twin's, with plain stores; the receiver
+ *               takes one 64-bit integer atomicAdd.  A lane walks a row of up to 8 slots, a wave one of up to 2048 with
+ *               16-byte loads, the workgroup a longer one; in the latter two the stored-order rule is an exclusive prefix
+ *               sum of the admissible residuals (a wave scan, no atomics among the lanes).
+ *      relabel  every evaluated vertex and every receiver adds what it received to its excess.  An evaluated vertex that
+ *               still has excess takes 1 + the minimum height over its residual arcs: read from the round's array, written
+ *               to the next round's.  The pass also queues the next round's vertices; appends are staged per wave in LDS and
+ *               reserved with one atomic per batch.
+ *      The queue's order may differ from run to run.  Nothing else does: every decision reads the round's snapshot.
+ *   3. Global relabeling inside the same launch: a level-synchronous backward BFS from the sink over residual arcs gives exact
+ *      heights; with F asked a second one from the source, offset by n, labels what cannot reach the sink; the rest gets the
+ *      limit (n without F, 2 n with it) and is not evaluated.  It runs before the first round and whenever n vertices have
+ *      been evaluated since the last time: a function of the inputs and the round alone, never of timing or the CU count.
+ *   4. The loop ends when the queue is empty.  Without F that is when no vertex with excess has a height below n, so none
+ *      reaches the sink: the preflow is maximum.  With F every vertex with excess stays in the loop (heights up to 2 n), so
+ *      the remaining excess returns to the source and the preflow becomes a flow.  value = the sink's excess; side = a last
+ *      backward BFS from the sink.
+ *   5. Plain launches make the outputs: one pass over A's entries for cut_arcs, cut_capacity and sink_side; F by flags, the
+ *      library's scan and a write with values max(0, capacity - residual) at A's positions, as select does.  No sort: A's
+ *      columns are ascending.  The host reads one record.
+ * What bounds it: heights never exceed 2 n, and the kernel leaves with the panic flag if one would; a BFS has at most n
+ * levels; the rounds are bounded by 8 n^2 + 4 n + 64 (and by 2^31).  Working memory: 44 bytes per vertex, 16 bytes per
+ * residual slot (at most 2 nvals + 3 n slots) and with F 4 bytes per entry of A, one allocation made before the first kernel
+ * and freed before the call returns; nothing is allocated inside the loop.  Unlike the other one-launch drivers, the working
+ * memory is proportional to nvals: the reverse arcs and the residuals have to live somewhere.  The worst case is a long thin
+ * network: a round moves the excess one arc and a global relabeling takes as many barrier-bound passes as the network is deep.
+ *
+ * value, arcs, flow_arcs, sink_side, cut_arcs and cut_capacity are exact and do not depend on scheduling; rounds,
+ * global_relabels, passes and loop_ms are for the bench only.
+ *
+ * Every error is found before F or side is written, and both keep what they held.  A null or unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, F not n x n, size(side) != n: GRB_DIMENSION_MISMATCH; source or sink outside
+ * 0 .. n - 1: GRB_INDEX_OUT_OF_BOUNDS (n = 0 cannot name two terminals, so it falls under this rule); source == sink, a mode
+ * outside 0..1, a bad capacity: GRB_INVALID_VALUE; A outside f32 / i32, or side not i32: GRB_NOT_IMPLEMENTED; F not of A's
+ * type: GRB_DOMAIN_MISMATCH; an A without a CSC of its own (a product result, the CSR-only format): GRB_INVALID_OBJECT; more
+ * than INT32_MAX residual slots: GRB_OUT_OF_MEMORY, as grb_matrix_extract answers an oversized result; a failed device
+ * allocation: GRB_OUT_OF_MEMORY; a grid barrier that gave up: GRB_PANIC.  No path from source to sink is a success with value
+ * 0, an empty F and side = the vertices that reach the sink. */
+#define GRB_FLOW_CAPACITY 0
+#define GRB_FLOW_UNIT 1
+typedef struct {
+  int64_t value;            /* the maximum flow value                                                */
+  int64_t arcs;             /* stored off-diagonal entries of A                                      */
+  int64_t flow_arcs;        /* nvals(F); -1 when F is NULL                                           */
+  int64_t sink_side;        /* vertices with side = 1                                                */
+  int64_t cut_arcs;         /* arcs from side 0 to side 1                                            */
+  int64_t cut_capacity;     /* their capacities, summed after the loop: always equal to value        */
+  int32_t rounds;           /* push-relabel rounds: implementation-defined, for the bench only       */
+  int32_t global_relabels;  /* global relabelings: implementation-defined, bench only                */
+  int32_t passes;           /* grid-wide passes the device ran: implementation-defined, bench only   */
+  int32_t launches;         /* kernel launches of the loop itself: 1                                 */
+  float   loop_ms;          /* HIP-event time of the call's device work                              */
+} grb_maxflow_result;        /* 72 bytes */
+grb_info grb_maxflow(grb_matrix F, grb_vector side, grb_matrix A, int64_t source, int64_t sink, int mode, grb_descriptor desc,
+                     grb_maxflow_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
