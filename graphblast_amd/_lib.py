@@ -87,6 +87,12 @@ class MaxflowResult(C.Structure):
                 ("passes", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
 
 
+class BccResult(C.Structure):
+    _fields_ = [("edges", C.c_int64), ("largest", C.c_int64), ("blocks", C.c_int32), ("bridges", C.c_int32),
+                ("articulation", C.c_int32), ("components", C.c_int32), ("isolated", C.c_int32), ("levels", C.c_int32),
+                ("rounds", C.c_int32), ("passes", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
+
+
 class TcCoreResult(C.Structure):
     _fields_ = [("core_rows", C.c_int32), ("min_row_length", C.c_int32), ("core_entries", C.c_int64), ("count", C.c_int64),
                 ("checksum", C.c_uint64), ("build_ms", C.c_float), ("product_ms", C.c_float), ("tiles", C.c_int32),
@@ -260,6 +266,7 @@ _SIGS = {
     "grb_relabel": [_vp, _vp, _i, C.POINTER(C.c_int32), _vp],
     "grb_contract": [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(ContractResult)],
     "grb_maxflow": [_vp, _vp, _vp, C.c_int64, C.c_int64, _i, _vp, C.POINTER(MaxflowResult)],
+    "grb_bcc": [_vp, _vp, _vp, _i, _vp, C.POINTER(BccResult)],
     "grb_tc_set_product": [_i],
     "grb_tc_release": [_vp],
     "grb_tc_last": [C.POINTER(TcInfo)],

@@ -984,6 +984,36 @@ def maxflow(F, side, A, source, sink, mode, desc):
                       launches=res.launches, loop_ms=res.loop_ms)
 
 
+GRB_BCC_BLOCKS, GRB_BCC_BRIDGES = 0, 1
+
+
+def bcc(Cm, art, A, mode, desc):
+    """grb_bcc: the biconnected components (blocks), articulation points and bridges of A's undirected graph.  A is n x n,
+    f32 or i32, symmetric in structure; its values are never read (a stored zero is an edge) and its diagonal takes no part.
+    A block is a class of "two edges lie on a common simple cycle, or are equal", a bridge a block of one edge; every edge is
+    in exactly one block.  The blocks are numbered 0 .. blocks-1 in ascending order of their smallest edge key
+    (min(u, v), max(u, v)), compared lexicographically, so the numbering is unique and the same inputs give the same bits.
+    Cm is None or n x n and i32 whatever A's type: with mode = GRB_BCC_BLOCKS = 0 it receives A's off-diagonal structure,
+    both directions, each entry's value the block number of that edge; with GRB_BCC_BRIDGES = 1 only the entries whose block
+    is a single edge, with the same numbers (columns ascending, empty rows for isolated vertices, CSC = a copy of the CSR
+    unless Cm is CSR only); Cm may be A when A is i32.  art is None or an i32 vector of size n that becomes dense: art[v] = the
+    number of blocks that contain v, 0 without an off-diagonal entry, >= 2 exactly at the articulation points.
+    Both may be None: only the record is filled.  No descriptor field is read.  Tarjan-Vishkin on a BFS forest as one launch on the
+    device; the passes grow with the BFS depth.  Only the CSR is read: with a CSC of its own an A whose structure is not
+    symmetric -> GrB_INVALID_VALUE, without one (a product result, the CSR-only format) the caller vouches for it and the
+    call stays bounded.  A mode outside {0, 1} -> GrB_INVALID_VALUE.  A null or unbuilt A -> GrB_UNINITIALIZED_OBJECT; A not
+    square, Cm not n x n or art not of size n -> GrB_DIMENSION_MISMATCH; A outside f32 / i32 or art not i32 ->
+    GrB_NOT_IMPLEMENTED; Cm not i32 -> GrB_DOMAIN_MISMATCH; no device memory -> GrB_OUT_OF_MEMORY; a grid barrier that gave up
+    -> GrB_PANIC (Cm and art unchanged on every error).  Returns (info, dict(edges, largest = edges of the largest block,
+    blocks, bridges, articulation = vertices with art >= 2, components, isolated, levels = depth of the BFS forest + 1,
+    rounds, passes = what the device ran, for the bench only, launches, loop_ms))."""
+    res = _lib.BccResult()
+    info = _lib.load().grb_bcc(_h(Cm), _h(art), _h(A), int(mode), _h(desc), C.byref(res))
+    return info, dict(edges=res.edges, largest=res.largest, blocks=res.blocks, bridges=res.bridges,
+                      articulation=res.articulation, components=res.components, isolated=res.isolated, levels=res.levels,
+                      rounds=res.rounds, passes=res.passes, launches=res.launches, loop_ms=res.loop_ms)
+
+
 def tc_set_product(on):
     """grb_tc_set_product: 0 = grb_tc counts without the product where that is a count and pays (default), 1 = always the
     product in B, 2 = the count wherever it is a count; < 0 queries."""

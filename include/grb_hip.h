@@ -1495,6 +1495,101 @@ typedef struct {
 grb_info grb_maxflow(grb_matrix F, grb_vector side, grb_matrix A, int64_t source, int64_t sink, int mode, grb_descriptor desc,
                      grb_maxflow_result* result);
 
+/* Biconnected components, articulation points and bridges (csrc/bcc.hip): grb_bcc.  The reference has no such driver
+ * (graphblas/algorithm/), so the definition is this header's own; LAGraph does not ship the algorithm either.
+ *
+ * A is n x n, f32 or i32.  Its structure is symmetric.  Its values are never read, so a stored zero is an edge.  Diagonal
+ * entries take no part.
+ *   G      = the simple undirected graph of A's off-diagonal entries
+ *   block  = a class of the relation "two edges lie on a common simple cycle, or are equal".  A bridge is a block of one
+ *            edge.  Every edge is in exactly one block.
+ *   key    = (min(u, v), max(u, v)) of the edge {u, v}, compared lexicographically.  The blocks are 0 .. blocks-1,
+ *            numbered in ascending order of their smallest edge key.  That numbering is unique, so the same inputs give the
+ *            same bits on any number of CUs.
+ *   art(v) = the number of blocks that contain v: 0 for a vertex without an off-diagonal entry, 1 for an ordinary vertex,
+ *            2 or more exactly when v is an articulation point.  It is v's degree in the block-cut tree.
+ *
+ * grb_bcc(C, art, A, mode, desc, result):
+ *   C      may be NULL.  Otherwise n x n and i32, whatever A's type; any other type is GRB_DOMAIN_MISMATCH.
+ *          GRB_BCC_BLOCKS:  C gets A's off-diagonal structure, both directions; the value is the block number of that edge.
+ *                           Columns ascend, and isolated vertices have empty rows.
+ *          GRB_BCC_BRIDGES: C gets only the entries whose block is a single edge, with the same block numbers as in
+ *                           GRB_BCC_BLOCKS mode.
+ *          The CSC is a copy of the CSR, unless C is in the CSR-only format.  C may be A when A is i32.
+ *   art    may be NULL.  Otherwise an i32 vector of size n that becomes dense.
+ *   desc   may be NULL; no descriptor field is read.  result may be NULL.  C and art may both be NULL: only the record is
+ *          filled.
+ *
+ * Structure (the rule of grb_kcore / grb_msf): only the CSR is read.  When A has a CSC of its own, one comparison on the
+ * device before the loop checks pointers and indices; a mismatch is GRB_INVALID_VALUE.  An A without a CSC of its own (a
+ * product result, the CSR-only matrix format) is taken on the caller's word: whatever it holds, nothing is read or written
+ * out of bounds and the call returns -- the levels are bounded by n, the hooking rounds by n + 1 each, every pointer-jumping
+ * loop by 40 passes, every column and every preorder number is checked before it is used as an index, and a vertex joins the
+ * queue once -- and the output is then unspecified.
+ *
+ * How: Tarjan-Vishkin on a BFS forest, as ONE co-resident launch of a 1024-thread workgroup per CU (GRB_NUM_CU is honoured)
+ * whose passes are separated by a grid barrier with bounded spins; the host reads one record at the end, so launches is 1
+ * whatever the graph.  A BFS forest and not an arbitrary spanning forest: its levels make subtree sizes, preorder numbers and
+ * low / high plain level-synchronous sweeps (no Euler tour, no list ranking), and a non-tree edge of a BFS tree never joins an
+ * ancestor with a descendant.  No floating point appears anywhere.
+ *   1. comp(v) = the smallest member of v's connected component: every off-diagonal entry hooks the larger of its ends'
+ *      labels (the label's slot and the end itself, atomicMin) onto the smaller, then pointer jumping (up to 16 labels a
+ *      vertex and pass), until a round finds every entry's ends agreed.  Rows are walked by a lane up to 8 entries, by a wave
+ *      with 16-byte index loads up to 2048, by the workgroup beyond, here and in every row pass below.
+ *   2. The vertices with comp(v) = v are the roots and all start at level 0.  ONE queue holds every vertex in level order with
+ *      an offset per level.  A level's vertices walk their rows: an unseen neighbour is claimed by a compare-and-swap of its
+ *      level and appended (staged per wave in LDS, one reservation per batch), and every neighbour on the next level takes an
+ *      atomicMin of the vertex: parent(w) = the smallest-numbered neighbour on the level above, so the forest repeats.
+ *   3. size(v), bottom-up by level: children add into their parent (integer atomicAdd).
+ *   4. pre(v), top-down by level.  The roots take consecutive ranges of one counter, so pre is a permutation of 0 .. n-1 and
+ *      names the tree edge (parent(w), w) as slot pre(w).  A child takes pre(parent) + 1 + its parent's cursor and adds its
+ *      size to the cursor: the order of siblings is the order of those atomics.  Every preorder gives the same blocks; the
+ *      order reaches nothing that leaves the call except rounds and passes.
+ *   5. low(v) / high(v) = min / max of pre(v) and of pre(w) over the non-tree edges {v, w}, over v's subtree: a row walk,
+ *      then bottom-up by level with atomicMin / atomicMax into the parent.
+ *   6. The auxiliary graph over the slots: (i) a non-tree edge {v, w} joins pre(v) with pre(w); (ii) for v = parent(w), v not
+ *      a root, pre(w) joins pre(v) when low(w) < pre(v) or high(w) >= pre(v) + size(v).  Its components by the same minimum
+ *      hooking and jumping as in 1, on pre, to the fixpoint: a block's representative is its tree edge of smallest pre, a
+ *      child of the block's top vertex.
+ *   7. The block of a tree edge is the label of its child's slot, of a non-tree edge the label of the end with the larger
+ *      pre.  Per representative an atomicMin of the CSR position over its entries with i < j (rows ascend: position order is
+ *      key order) and their count, a thread handing over a run of equal representatives at once.  art(v) = [v is not a root]
+ *      + the children c of v whose slot is its own label.  largest, bridges, articulation: integer counts per representative.
+ * After the loop the representatives' (smallest position, slot) pairs go through the library's radix sort, at most n of
+ * them: a block's number is its rank.  C is a count per row, the library's scan and one writing pass (a wave a row, stored
+ * order); GRB_BCC_BRIDGES keeps the entries of blocks with one entry above the diagonal.
+ * Working memory: 76 bytes per vertex and 2.5 KiB, one allocation made before the kernel and freed before the call returns;
+ * nothing is allocated inside the loop and nothing is proportional to nvals.  The sort brings 12 bytes per block of its own.
+ * Passes: four per BFS level (expansion, size, pre, low / high) plus the hooking rounds and their jumps.  Known worst case: a
+ * path of a million vertices costs millions of barrier-bound passes, as a long path does in grb_scc.
+ *
+ * edges, largest, blocks, bridges, articulation, components, isolated and levels are exact and do not depend on scheduling;
+ * rounds and passes are for the bench only.
+ *
+ * Every error is found before C or art is written, and both keep what they held.  A null or unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square, C not n x n, size(art) != n: GRB_DIMENSION_MISMATCH; A outside f32 / i32, or art not
+ * i32: GRB_NOT_IMPLEMENTED; C not i32: GRB_DOMAIN_MISMATCH; a mode outside {0, 1}, or an asymmetric A (with a CSC of its own):
+ * GRB_INVALID_VALUE; a failed device allocation: GRB_OUT_OF_MEMORY; a grid barrier that gave up: GRB_PANIC.  n = 0 is a success
+ * with a zero record.  An A without off-diagonal entries is a success with an empty C, art = 0 everywhere, blocks = 0 and
+ * components = isolated = n. */
+#define GRB_BCC_BLOCKS  0
+#define GRB_BCC_BRIDGES 1
+typedef struct {
+  int64_t edges;         /* undirected edges of G                                            */
+  int64_t largest;       /* edges of the largest block; 0 without edges                      */
+  int32_t blocks;        /* biconnected components, bridges included                         */
+  int32_t bridges;       /* blocks of one edge                                               */
+  int32_t articulation;  /* vertices with art(v) >= 2                                        */
+  int32_t components;    /* connected components of G, isolated vertices included            */
+  int32_t isolated;      /* vertices without an off-diagonal entry                           */
+  int32_t levels;        /* depth of the BFS forest + 1; 0 when n = 0                        */
+  int32_t rounds;        /* hooking rounds: implementation-defined, for the bench only       */
+  int32_t passes;        /* grid-wide passes: implementation-defined, for the bench only     */
+  int32_t launches;      /* kernel launches of the loop itself: 1                            */
+  float   loop_ms;       /* HIP-event time of the call's device work                         */
+} grb_bcc_result;         /* 56 bytes */
+grb_info grb_bcc(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_descriptor desc, grb_bcc_result* result);
+
 /* ---- The remaining drivers of graphblas/algorithm/  and the two extension
  * operations only they use. */
 /* scatter   operations.hpp:748-761 -> backend :1110-1142 (scatter.hpp:10-82): w[(Index)u[k]] = val
