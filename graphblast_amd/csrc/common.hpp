@@ -530,6 +530,17 @@ grb_info wait_granules(int seq, int count, unsigned int* out);
 
 // ----------------------------------------------------------------------------
 // Objects behind the handles
+// nonzeros per wave tile of the SpMV plan (8 per lane, 2 KiB of LDS per wave): build_spmv_plan cuts by it, and every kernel
+// that walks the plan's tiles (spmv.hip, spmm.hip) sizes its LDS staging and its index arithmetic by it.  A tuning knob
+// of the SpMV kernel (tools/build_spmv_variants.sh builds A/B variants).
+#ifndef GRB_HUB_TILE
+#define GRB_HUB_TILE 512
+#endif
+constexpr int kWaveTile = GRB_HUB_TILE;
+static_assert(kWaveTile >= kWave && (kWaveTile & (kWaveTile - 1)) == 0 && kWaveTile % kWave == 0,
+              "the wave tile is a power of two (entries are found by & (kWaveTile - 1)) and a multiple of the wave "
+              "(it is loaded in kWaveTile / kWave steps of one entry per lane)");
+
 struct SpmvBlock {        // one wave tile of an SpMV
   int row_start, row_end; // rows [row_start, row_end)
   int nnz_start, nnz_end; // their nonzeros (or a slice of one long row)

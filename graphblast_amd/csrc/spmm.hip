@@ -22,7 +22,7 @@
 
 namespace grb {
 
-constexpr int kSpmmTile = 512;        // must equal the SpMV plan's wave tile
+// the tiles are those of the SpMV plan: kWaveTile (common.hpp) entries at most, staged in LDS per wave
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -37,8 +37,8 @@ __global__ __launch_bounds__(kBlock) void spmm_tile_kernel(const SpmvBlock* __re
                                                            Index col0) {
   typedef Semiring<SR, T> S;
   constexpr int G = kWave / KG;
-  __shared__ Index s_ci[kWavesPerBlock][kSpmmTile];
-  __shared__ T s_cv[kWavesPerBlock][kSpmmTile];
+  __shared__ Index s_ci[kWavesPerBlock][kWaveTile];
+  __shared__ T s_cv[kWavesPerBlock][kWaveTile];
   const int lane = lane_id();
   const int grp = lane / KG;
   const Index c = col0 + (lane % KG);
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void spmm_tile_kernel(const SpmvBlock* __re
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int j = 0; j < kSpmmTile / kWave; ++j) {
+    for (int j = 0; j < kWaveTile / kWave; ++j) {
       const int at = j * kWave + lane;
       // an all-empty tile (trailing empty rows) starts AT the end of the arrays: nothing of it may be read
       const int q = cnt > 0 ? blk.nnz_start + (at < cnt ? at : 0) : 0;
@@ -63,8 +63,8 @@ __global__ __launch_bounds__(kBlock) void spmm_tile_kernel(const SpmvBlock* __re
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     auto entry = [&](int at, Index* col, T* v) {
-      *col = s_ci[wave_id()][at & (kSpmmTile - 1)];
-      *v = s_cv[wave_id()][at & (kSpmmTile - 1)];
+      *col = s_ci[wave_id()][at & (kWaveTile - 1)];
+      *v = s_cv[wave_id()][at & (kWaveTile - 1)];
     };
     const bool slice = blk.slot >= 0;
     for (int r0 = blk.row_start; r0 < blk.row_end; r0 += G) {

@@ -31,9 +31,6 @@ namespace grb {
 #ifndef GRB_HUB_THREADS
 #define GRB_HUB_THREADS 1024
 #endif
-#ifndef GRB_HUB_TILE
-#define GRB_HUB_TILE 512
-#endif
 #ifndef GRB_HUB_HOT
 #define GRB_HUB_HOT 32768
 #endif
@@ -42,7 +39,7 @@ namespace grb {
 #endif
 constexpr int kHubThreads = GRB_HUB_THREADS;   // one workgroup per CU owning all 160 KiB of LDS
 constexpr int kHubWaves = kHubThreads / kWave;
-constexpr int kWaveTile = GRB_HUB_TILE;   // nonzeros per wave tile (8 per lane), 2 KiB of LDS per wave
+// kWaveTile (GRB_HUB_TILE), the nonzeros per wave tile, lives in common.hpp: spmm.hip walks the same tiles
 constexpr int kWaveRows = 64;       // rows per wave tile: lane r carries the pointers of row r
 constexpr int kHot = GRB_HUB_HOT;   // leading values of the packed vector kept in LDS (128 KiB)
 constexpr int kHubPerCu = 163840 / (4 * kHot + 4 * kHubWaves * kWaveTile);
