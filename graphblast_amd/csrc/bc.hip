@@ -24,7 +24,7 @@
 // same inputs give the same bits.  Nothing is allocated inside the loops.  The host reads the list offsets once every
 // kBcChunk levels of the sweep (launching a level past the last one costs two empty launches), and nothing else; the
 // backward levels are launched back to back with grids of their lists' sizes.
-#include "common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -202,14 +202,6 @@ __global__ __launch_bounds__(kBlock) void bc_round_kernel(const double* __restri
 
 namespace {
 
-struct BcEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~BcEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 inline int bc_grid(u64 items, Index n) {
   u64 g = items < (u64)kBcGrid ? items : (u64)kBcGrid;
   if (g > (u64)n) g = (u64)n;
@@ -223,9 +215,8 @@ grb_info bc_run(grb_vector bc, grb_matrix A, const std::vector<Index>& src, grb_
   const int ns = (int)src.size();
   grb_bc_result out = {};
   out.sources = ns;
-  BcEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- everything the call needs, up front
   const size_t rows = (size_t)n * kBcBatch, noff = (size_t)n + kBcChunk + 8;
   EwmBuf b_depth, b_sigma, b_list, b_small;
@@ -242,13 +233,7 @@ grb_info bc_run(grb_vector bc, grb_matrix A, const std::vector<Index>& src, grb_
   u64* d_info = d_off + noff;
   int* d_mark = (int*)(d_info + 2);
   Index* d_src = (Index*)(d_mark + n);
-  const int old_type = bc->vec_type;
-  const grb_info si = grb_vector_set_storage(bc, GRB_DENSE);   // allocates only where bc has no dense storage yet
-  if (si != GRB_SUCCESS || !bc->d_val) {
-    bc->vec_type = old_type;
-    return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
-  }
-  bc->vec_type = old_type;                               // bc is as it was until the result is there
+  GRB_TRY(dense_out_prepare(bc, n));                     // bc is as it was until the result is there (bc_round_kernel writes it)
   GRB_HIP_TRY(hipMemsetAsync(d_acc, 0, 8 * (size_t)n, s));
   GRB_HIP_TRY(hipMemsetAsync(d_info, 0, 16, s));
   GRB_HIP_TRY(hipMemcpyAsync(d_src, src.data(), sizeof(Index) * (size_t)ns, hipMemcpyHostToDevice, s));

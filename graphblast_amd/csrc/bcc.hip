@@ -31,7 +31,7 @@
 // proportional to the entries.
 // Passes: 4 per BFS level (expansion, size, pre, low/high) + a hooking round's 1 + its jumps, for both hookings.  A path of a
 // million vertices costs millions of barrier-bound passes: the known worst case, as a long path is in scc.hip.
-#include "persist_common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -54,7 +54,7 @@ struct BcState {                    // zeroed by the host before the launch
   unsigned prebase[32];             // the roots' ranges of pre
   unsigned nrep[32];                // representatives listed
   unsigned largest[32];             // entries of the largest block
-  unsigned flag[32];                // bc_compare_kernel: 1 = the CSR and the CSC differ
+  unsigned flag[32];                // the symmetry check (graph_common.hpp): 1 = the CSR's and the CSC's structures differ
   unsigned long long rec[kBcRec];   // [0] off-diagonal entries [1] largest [2] blocks [3] bridges [4] articulation [5] components
                                     // [6] isolated [7] levels [8] rounds [9] passes [10] done
 };
@@ -68,18 +68,6 @@ struct BcArgs {
   unsigned* pay;                    // ... and slot
   BcState* st;
 };
-
-// flag |= 1 when the CSR's and the CSC's structures differ: pointers and indices (the values are never read)
-__global__ __launch_bounds__(kBlock) void bc_compare_kernel(const Index* __restrict__ a_ptr, const Index* __restrict__ b_ptr, long long n1,
-                                                            const Index* __restrict__ a_ind, const Index* __restrict__ b_ind, long long nnz,
-                                                            unsigned int* __restrict__ flag) {
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n1 + nnz; i += (long long)gridDim.x * kBlock) {
-    if (i < n1) bad |= a_ptr[i] != b_ptr[i];
-    else bad |= a_ind[i - n1] != b_ind[i - n1];
-  }
-  if (__ballot(bad) != 0ull && lane_id() == 0) atomicOr(flag, 1u);
-}
 
 // minimum hooking of the edge (x, y) in the label array L (L[i] <= i, always a member of i's component): the larger label's
 // slot and the end that held it take the smaller label.  false: the two agree already
@@ -109,12 +97,9 @@ struct BcLds {
 // called by every lane of a wave together
 template <int kThreads, typename F>
 __device__ __forceinline__ void bc_walk(const BcArgs& a, Index v, Index b, Index e, int t, F& f) {
-  // up to three entries before the first 16-byte boundary, whole quads, up to three entries behind them
-  Index b4 = b + (Index)((4u - (unsigned)((reinterpret_cast<uintptr_t>(a.ind + b) >> 2) & 3u)) & 3u);
-  if (b4 > e) b4 = e;
-  const Index nq = (e - b4) >> 2, te = b4 + 4 * nq;
+  const QuadSpan s = quad_span(a.ind, b, e);
+  const Index b4 = s.b4, nq = s.nq, te = s.te, nh = s.nh, ns = s.ns;
   if (kThreads == kWave || t < kWave) {
-    const Index nh = b4 - b, ns = nh + (e - te);
     const bool ok = t < ns;
     Index p = 0, u = 0;
     if (ok) {
@@ -333,18 +318,6 @@ struct BcCount {
   __device__ __forceinline__ void end(Index, bool, bool) {}
 };
 
-// the length of v's row without a stored diagonal (indices ascending)
-__device__ __forceinline__ int bc_degree(const BcArgs& a, Index v) {
-  const Index b = a.ptr[v], e = a.ptr[v + 1];
-  Index lo = b, hi = e;
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a.ind[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  const int d = (int)(e - b) - (lo < e && a.ind[lo] == v ? 1 : 0);
-  return d > 0 ? d : 0;
-}
-
 __global__ __launch_bounds__(kPThreads) void bcc_persistent_kernel(BcArgs a) {
   __shared__ BcLds S;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
@@ -421,7 +394,7 @@ __global__ __launch_bounds__(kPThreads) void bcc_persistent_kernel(BcArgs a) {
     unsigned long long my_sum = 0;
     pass_begin();
     for (long long v = gtid; v < n; v += gthreads) {
-      const int d = bc_degree(a, (Index)v);
+      const int d = row_degree_no_diag(a.ptr, a.ind, (Index)v);
       publish(&a.comp[v], (int)v);
       publish(&a.lab[v], (int)v);
       publish(&a.level[v], -1);
@@ -709,53 +682,21 @@ __global__ __launch_bounds__(kBlock) void bc_rows_kernel(BcArgs a, int bridges_o
 
 namespace {
 
-struct BcEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~BcEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
-inline int bc_bits(long long dim) {
-  int b = 1;
-  while (b < 32 && ((long long)1 << b) < dim) ++b;
-  return b;
-}
-
-// C's arrays for m entries, exactly
-grb_info bc_side(Side* sd, Index n, long long m) {
-  GRB_TRY(ewm_alloc(&sd->ptr, 4 * ((size_t)n + 1)));
-  GRB_TRY(ewm_alloc(&sd->ind, 4 * (size_t)(m > 0 ? m : 1)));
-  GRB_TRY(ewm_alloc(&sd->val, 4 * (size_t)(m > 0 ? m : 1)));
-  sd->nnz = (Index)m;
-  sd->h_ptr.assign((size_t)n + 1, 0);
-  return GRB_SUCCESS;
-}
-
 grb_info bcc_run(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_bcc_result* res) {
   GRB_TRY(ctx_init());
   Context& c = ctx();
   hipStream_t s = c.stream;
   const Index n = A->nrows;
-  const bool own_csc = !A->csc_alias && A->csc.ptr != nullptr;
   const bool both = C && C->format != 1;
   grb_bcc_result r = {};
   Side sr, sc;
-  if (n > 0) {
-    static int max_per_cu = 0;
-    if (!max_per_cu) {
-      GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, bcc_persistent_kernel, kPThreads, 0));
-      if (max_per_cu < 1) return GRB_PANIC;
-    }
-  }
-  BcEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  if (n > 0) GRB_TRY(persistent_kernel_fits(bcc_persistent_kernel));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- one allocation: the state, sixteen words per vertex (lvoff has n + 2), the representatives' pairs, the scan's totals
-  const size_t st_bytes = (sizeof(BcState) + 255) & ~(size_t)255;
-  const size_t vw = ((size_t)n + 2 + 63) & ~(size_t)63;
-  const size_t scan_bytes = (device_scan_u32_scratch((long long)n + 1) + 63) & ~(size_t)63;
+  const size_t st_bytes = pad_bytes(sizeof(BcState));
+  const size_t vw = pad_words((size_t)n + 2);
+  const size_t scan_bytes = (device_scan_u32_scratch((long long)n + 1) + 63) & ~(size_t)63;   // (the last array: to 64 bytes)
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, st_bytes + 76 * vw + scan_bytes + 64));
   BcArgs a;
@@ -782,21 +723,13 @@ grb_info bcc_run(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_bcc_r
   int* d_number = a.art + vw;                            // a representative's block number
   unsigned* d_counts = (unsigned*)(d_number + vw);       // C's entries per row, then its pointers
   unsigned* d_scan = d_counts + vw;
-  // art's dense storage, before anything runs (allocates only where it has none yet); it stays as it was until the end
-  if (art) {
-    const int old_type = art->vec_type;
-    const grb_info si = grb_vector_set_storage(art, GRB_DENSE);
-    art->vec_type = old_type;
-    if (si != GRB_SUCCESS || (n > 0 && !art->d_val)) return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
-  }
+  if (art) GRB_TRY(dense_out_prepare(art, n));           // before anything runs; art stays as it was until the end
   long long B = 0, m = 0;
   if (n > 0) {
     GRB_TRY(bfs_lanes_fence(s));    // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
     GRB_HIP_TRY(hipEventRecord(ev.a, s));
     GRB_HIP_TRY(hipMemsetAsync(work.p, 0, st_bytes, s));
-    if (own_csc)
-      hipLaunchKernelGGL(bc_compare_kernel, dim3(stream_grid((long long)n + 1 + (long long)A->nvals)), dim3(kBlock), 0, s, A->csr.ptr, A->csc.ptr,
-                         (long long)n + 1, A->csr.ind, A->csc.ind, (long long)A->nvals, &a.st->flag[0]);
+    launch_symmetry_check<false>(A, &a.st->flag[0], s);  // (the values are never read)
     hipLaunchKernelGGL(bcc_persistent_kernel, dim3(c.num_cu), dim3(kPThreads), 0, s, a);
     GRB_HIP_TRY(hipGetLastError());
     struct { unsigned flag[32]; unsigned long long rec[kBcRec]; } h;
@@ -821,7 +754,7 @@ grb_info bcc_run(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_bcc_r
   // ---- C's arrays: the blocks' numbers, a count per row, the scan, one writing pass
   if (C) {
     if (n > 0) {
-      GRB_TRY(device_sort_pairs(a.keys, a.pay, B, bc_bits((long long)A->nvals + 1), 0));
+      GRB_TRY(device_sort_pairs(a.keys, a.pay, B, key_bits((long long)A->nvals + 1), 0));
       if (B > 0) hipLaunchKernelGGL(bc_number_kernel, dim3(stream_grid(B)), dim3(kBlock), 0, s, a.pay, B, n, d_number);
       GRB_HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * ((size_t)n + 1), s));
       hipLaunchKernelGGL(bc_rows_kernel<false>, dim3(stream_grid((long long)n * kWave)), dim3(kBlock), 0, s, a, mode, d_number, d_counts,
@@ -832,8 +765,8 @@ grb_info bcc_run(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_bcc_r
       GRB_HIP_TRY(hipMemcpy(&total, d_counts + n, 4, hipMemcpyDeviceToHost));
       m = (long long)total;
     }
-    GRB_TRY(bc_side(&sr, n, m));
-    if (both) GRB_TRY(bc_side(&sc, n, m));
+    GRB_TRY(side_alloc(&sr, n, m));
+    if (both) GRB_TRY(side_alloc(&sc, n, m));
     if (n > 0) {
       GRB_HIP_TRY(hipMemcpyAsync(sr.ptr.p, d_counts, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
       if (m > 0) {
@@ -842,13 +775,7 @@ grb_info bcc_run(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_bcc_r
         GRB_HIP_TRY(hipGetLastError());
       }
       GRB_HIP_TRY(hipMemcpyAsync(sr.h_ptr.data(), sr.ptr.p, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost, s));
-      if (both) {                                        // the structure is symmetric and an edge has one block: the CSC is a copy
-        GRB_HIP_TRY(hipMemcpyAsync(sc.ptr.p, sr.ptr.p, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
-        if (m > 0) {
-          GRB_HIP_TRY(hipMemcpyAsync(sc.ind.p, sr.ind.p, 4 * (size_t)m, hipMemcpyDeviceToDevice, s));
-          GRB_HIP_TRY(hipMemcpyAsync(sc.val.p, sr.val.p, 4 * (size_t)m, hipMemcpyDeviceToDevice, s));
-        }
-      }
+      if (both) GRB_TRY(side_mirror(&sc, sr, n, m, s));  // the structure is symmetric and an edge has one block: the CSC is a copy
     } else {
       GRB_HIP_TRY(hipMemsetAsync(sr.ptr.p, 0, 4, s));
       if (both) GRB_HIP_TRY(hipMemsetAsync(sc.ptr.p, 0, 4, s));
@@ -865,14 +792,7 @@ grb_info bcc_run(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_bcc_r
   // everything that can fail is behind us, but the CSC's plan (attach builds it before it touches C) and a copy.  A, which
   // may be C, has been read for the last time
   if (C) GRB_TRY(attach(C, &sr, both ? &sc : nullptr));
-  if (art) {
-    if (n > 0) {
-      GRB_HIP_TRY(hipMemcpyAsync(art->d_val, a.art, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-      GRB_HIP_TRY(hipStreamSynchronize(s));
-    }
-    art->vec_type = GRB_DENSE;
-    art->d_nnz = n;
-  }
+  if (art) GRB_TRY(dense_out_commit(art, a.art, n, s));
   if (res) *res = r;
   return GRB_SUCCESS;
 }

@@ -27,7 +27,7 @@
 //             changes every time, and the marks would be a third of the time), and only if it then changes fewer than n
 //             are the marks made after the fact, by one more kernel and one more host read.
 // The host reads one record per iteration: {changed, the five list lengths, evaluated}.  Nothing is allocated in the loop.
-#include "common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -396,17 +396,7 @@ namespace {
 
 int g_cd_skip = 1;
 
-struct CdEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~CdEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 inline int cd_grid(long long items) { return (int)((items + kBlock - 1) / kBlock > 0 ? (items + kBlock - 1) / kBlock : 1); }
-inline size_t cd_pad(size_t words) { return (words + 63) & ~(size_t)63; }   // every array begins on a 256-byte line
-
 grb_info cdlp_run(grb_vector labels, grb_matrix A, grb_vector init, bool directed, int max_iter, grb_cdlp_result* res) {
   GRB_TRY(ctx_init());
   hipStream_t s = ctx().stream;
@@ -415,11 +405,10 @@ grb_info cdlp_run(grb_vector labels, grb_matrix A, grb_vector init, bool directe
   const bool pull = !directed && !own_csc;               // nobody to push to: every task looks at its neighbours first
   const bool skip = g_cd_skip != 0;
   grb_cdlp_result out = {};
-  CdEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- two label arrays, two bitmaps, the five lists, the record: one allocation
-  const size_t lw = cd_pad((size_t)n), bw = cd_pad(((size_t)n + 31) / 32 + 1);
+  const size_t lw = pad_words((size_t)n), bw = pad_words(((size_t)n + 31) / 32 + 1);
   EwmBuf work, pool;
   GRB_TRY(ewm_alloc(&work, 4 * (2 * lw + 2 * bw + kCdClasses * lw + 64)));
   unsigned int* d_rec = (unsigned int*)work.p;           // [0..7] as CdArgs::rec, [8] a label out of range
@@ -465,13 +454,7 @@ grb_info cdlp_run(grb_vector labels, grb_matrix A, grb_vector init, bool directe
     GRB_TRY(ewm_alloc(&pool, 4 * (size_t)npool * (size_t)n));
     GRB_HIP_TRY(hipMemsetAsync(pool.p, 0, 4 * (size_t)npool * (size_t)n, s));
   }
-  const int old_type = labels->vec_type;
-  const grb_info si = grb_vector_set_storage(labels, GRB_DENSE);   // allocates only where labels has no dense storage yet
-  if (si != GRB_SUCCESS || !labels->d_val) {
-    labels->vec_type = old_type;
-    return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
-  }
-  labels->vec_type = old_type;                           // labels is as it was until the result is there
+  GRB_TRY(dense_out_prepare(labels, n));                 // labels is as it was until the result is there
   if (pull && skip) GRB_HIP_TRY(hipMemsetAsync(d_bits[0], 0xff, 4 * bw, s));   // iteration 1: everybody's neighbours "changed"
   // ---- the iterations
   GRB_HIP_TRY(hipEventRecord(ev.a, s));
@@ -534,10 +517,7 @@ grb_info cdlp_run(grb_vector labels, grb_matrix A, grb_vector init, bool directe
   GRB_HIP_TRY(hipGetLastError());
   GRB_HIP_TRY(hipMemcpyAsync(h_rec, d_rec, 32, hipMemcpyDeviceToHost, s));
   GRB_HIP_TRY(hipStreamSynchronize(s));                  // every kernel has run: nothing can fail from here on
-  GRB_HIP_TRY(hipMemcpyAsync(labels->d_val, d_lab[cur], 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-  GRB_HIP_TRY(hipStreamSynchronize(s));
-  labels->vec_type = GRB_DENSE;
-  labels->d_nnz = n;
+  GRB_TRY(dense_out_commit(labels, d_lab[cur], n, s));
   GRB_HIP_TRY(hipEventElapsedTime(&out.loop_ms, ev.a, ev.b));
   out.communities = (int32_t)h_rec[7];
   if (res) *res = out;

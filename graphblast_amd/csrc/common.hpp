@@ -376,6 +376,23 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   t = mx(t, __builtin_amdgcn_update_dpp(0u, t, 0x143, 0xc, 0xf, false));
   return (unsigned)__builtin_amdgcn_readlane((int)t, 63);
 }
+// 64-bit max of a wave, in every lane, and the 64-bit inclusive prefix sum over its lanes: six shuffle steps each
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+  for (int s = kWave / 2; s > 0; s >>= 1) {
+    const unsigned long long o = __shfl_xor(v, s, kWave);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long v) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const unsigned long long t = __shfl_up(v, (unsigned)o, kWave);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
 
 // Reduce within aligned groups of L lanes (L power of two <= 64).
 template <typename T, typename F>

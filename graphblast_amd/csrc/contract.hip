@@ -21,7 +21,7 @@
 // PLUS on f32 adds in f64 and rounds once; MINIMUM / MAXIMUM compare the monotone map of the bits and map the winner back, so
 // the winner's bits come out whatever the order; i32 PLUS wraps.  No floating-point atomic anywhere: the same inputs give the
 // same bits whatever the grid.  Every index read from map or A is checked against its array before it is used.
-#include "common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -35,15 +35,6 @@ enum { kCtBad = 0, kCtDropped, kCtKept, kCtLoops, kCtLong /* long runs << 32 | t
 template <int M> struct CtAcc { typedef unsigned type; };
 template <> struct CtAcc<CT_PLUS_F32> { typedef double type; };
 
-// the usual monotone map of a value's bits to an unsigned (f32: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN) and back
-__device__ __forceinline__ unsigned ct_order(unsigned b, int f32) {
-  if (!f32) return b ^ 0x80000000u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ unsigned ct_unorder(unsigned o, int f32) {
-  if (!f32) return o ^ 0x80000000u;
-  return (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-}
 template <int M>
 __device__ __forceinline__ typename CtAcc<M>::type ct_identity() {
   if constexpr (M == CT_PLUS_F32) return -0.0;           // (-0 + x = x for every x, -0 included)
@@ -53,7 +44,7 @@ __device__ __forceinline__ typename CtAcc<M>::type ct_identity() {
 template <int M>
 __device__ __forceinline__ typename CtAcc<M>::type ct_load(unsigned bits, int f32) {
   if constexpr (M == CT_PLUS_F32) return (double)__uint_as_float(bits);
-  else if constexpr (M == CT_MIN || M == CT_MAX) return ct_order(bits, f32);
+  else if constexpr (M == CT_MIN || M == CT_MAX) return value_order(bits, f32);
   else return bits;
 }
 template <int M>
@@ -65,7 +56,7 @@ __device__ __forceinline__ typename CtAcc<M>::type ct_combine(typename CtAcc<M>:
 template <int M>
 __device__ __forceinline__ unsigned ct_store(typename CtAcc<M>::type x, int f32) {
   if constexpr (M == CT_PLUS_F32) return __float_as_uint((float)x);
-  else if constexpr (M == CT_MIN || M == CT_MAX) return ct_unorder(x, f32);
+  else if constexpr (M == CT_MIN || M == CT_MAX) return value_unorder(x, f32);
   else return x;
 }
 template <int M>
@@ -306,15 +297,6 @@ __global__ __launch_bounds__(kBlock) void ct_sizes_kernel(const unsigned* __rest
 
 namespace {
 
-struct CtEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~CtEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
-inline size_t ct_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 inline int ct_sort_launches(int bits) { return 5 * ((bits + 7) / 8); }   // a histogram, the scan's three, a scatter per digit
 
 // the stored values of an i32 vector with every value stored, as n words on the device: its dense storage, or `tmp` filled
@@ -333,15 +315,6 @@ grb_info ct_dense_values(grb_vector u, Index n, int* tmp, hipStream_t s, const i
 inline Index ct_stored(const grb_vector_s* u) {
   return u->vec_type == GRB_DENSE ? u->nsize : u->vec_type == GRB_SPARSE ? u->s_nvals : 0;
 }
-// w's dense storage exists from here on (allocates only where it has none yet); it stays as it was until the call succeeds
-grb_info ct_want_dense(grb_vector w) {
-  const int old_type = w->vec_type;
-  const grb_info si = grb_vector_set_storage(w, GRB_DENSE);
-  w->vec_type = old_type;
-  if (si != GRB_SUCCESS) return si;
-  return w->nsize > 0 && !w->d_val ? GRB_OUT_OF_MEMORY : GRB_SUCCESS;
-}
-
 grb_info relabel_run(grb_vector map, grb_vector labels, int kind, int32_t* count) {
   GRB_TRY(ctx_init());
   hipStream_t s = ctx().stream;
@@ -353,7 +326,7 @@ grb_info relabel_run(grb_vector map, grb_vector labels, int kind, int32_t* count
     return GRB_SUCCESS;
   }
   // ---- one allocation: the record, the flags, the result, the labels of a sparse vector, the scan's totals
-  const size_t fw = ct_pad(4 * ((size_t)n + 1)), scan_bytes = ct_pad(device_scan_u32_scratch((long long)n + 1));
+  const size_t fw = pad_bytes(4 * ((size_t)n + 1)), scan_bytes = pad_bytes(device_scan_u32_scratch((long long)n + 1));
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, 256 + 3 * fw + scan_bytes));
   unsigned long long* d_rec = (unsigned long long*)work.p;
@@ -361,7 +334,7 @@ grb_info relabel_run(grb_vector map, grb_vector labels, int kind, int32_t* count
   int* d_out = (int*)((char*)d_flags + fw);
   int* d_tmp = (int*)((char*)d_out + fw);
   unsigned* d_totals = (unsigned*)((char*)d_tmp + fw);
-  GRB_TRY(ct_want_dense(map));
+  GRB_TRY(dense_out_prepare(map, n));
   GRB_HIP_TRY(hipMemsetAsync(work.p, 0, 256 + fw, s));
   const int* d_lab = nullptr;
   GRB_TRY(ct_dense_values(labels, n, d_tmp, s, &d_lab));
@@ -376,10 +349,7 @@ grb_info relabel_run(grb_vector map, grb_vector labels, int kind, int32_t* count
   GRB_HIP_TRY(hipMemcpyAsync(&nc, d_flags + n, 4, hipMemcpyDeviceToHost, s));
   GRB_HIP_TRY(hipStreamSynchronize(s));                  // the call's one read
   if (bad) return GRB_INVALID_INDEX;
-  GRB_HIP_TRY(hipMemcpyAsync(map->d_val, d_out, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-  GRB_HIP_TRY(hipStreamSynchronize(s));
-  map->vec_type = GRB_DENSE;
-  map->d_nnz = n;
+  GRB_TRY(dense_out_commit(map, d_out, n, s));
   if (count) *count = (int32_t)nc;
   return GRB_SUCCESS;
 }
@@ -406,16 +376,15 @@ grb_info contract_run(grb_matrix C, grb_vector sizes, grb_matrix A, grb_vector m
   const int f32 = A->dtype == GRB_F32 ? 1 : 0;
   const bool both = C->format != 1;
   grb_contract_result r = {};
-  CtEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  EventPair ev;
+  GRB_TRY(ev.create());
   int cb = 1;                                            // nc < 2^cb: a coarse id and the key of a dropped entry fit
   while (cb < 31 && ((long long)1 << cb) <= (long long)nc) ++cb;
   // ---- one allocation: the record, keys, the pieces' results, payloads, flags, starts, the long runs, map, sizes, the scan
   const unsigned cap = (unsigned)(Z / kCtLaneRun + 2);   // long runs and pieces, at most (a long run of len has <= len / 32 pieces)
-  const size_t kb = ct_pad(8 * (size_t)(Z + 1)), pb = ct_pad(8 * (size_t)cap), wb = ct_pad(4 * (size_t)(Z + 2)), lb = ct_pad(4 * (size_t)cap);
-  const size_t nb = ct_pad(4 * ((size_t)n + 1)), cbytes = ct_pad(4 * ((size_t)nc + 1));
-  const size_t scan_bytes = ct_pad(device_scan_u32_scratch(Z + 2));
+  const size_t kb = pad_bytes(8 * (size_t)(Z + 1)), pb = pad_bytes(8 * (size_t)cap), wb = pad_bytes(4 * (size_t)(Z + 2)), lb = pad_bytes(4 * (size_t)cap);
+  const size_t nb = pad_bytes(4 * ((size_t)n + 1)), cbytes = pad_bytes(4 * ((size_t)nc + 1));
+  const size_t scan_bytes = pad_bytes(device_scan_u32_scratch(Z + 2));
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, 256 + kb + pb + 3 * wb + 2 * lb + nb + cbytes + scan_bytes));
   char* q = (char*)work.p;
@@ -430,7 +399,7 @@ grb_info contract_run(grb_matrix C, grb_vector sizes, grb_matrix A, grb_vector m
   int* d_tmp = (int*)q; q += nb;
   unsigned* d_sizes = (unsigned*)q; q += cbytes;
   unsigned* d_totals = (unsigned*)q;
-  if (sizes) GRB_TRY(ct_want_dense(sizes));
+  if (sizes) GRB_TRY(dense_out_prepare(sizes, nc));
   Side sr, sc;
   GRB_TRY(ewm_alloc(&sr.ptr, 4 * ((size_t)nc + 1)));
   sr.h_ptr.assign((size_t)nc + 1, 0);
@@ -535,14 +504,7 @@ grb_info contract_run(grb_matrix C, grb_vector sizes, grb_matrix A, grb_vector m
   // everything that can fail is behind us, but the CSC's plan (attach builds it before it touches C) and one copy.  A, which
   // may be C, has been read for the last time
   GRB_TRY(attach(C, &sr, both ? &sc : nullptr));
-  if (sizes) {
-    if (nc > 0) {
-      GRB_HIP_TRY(hipMemcpyAsync(sizes->d_val, d_sizes, 4 * (size_t)nc, hipMemcpyDeviceToDevice, s));
-      GRB_HIP_TRY(hipStreamSynchronize(s));
-    }
-    sizes->vec_type = GRB_DENSE;
-    sizes->d_nnz = nc;
-  }
+  if (sizes) GRB_TRY(dense_out_commit(sizes, d_sizes, nc, s));
   if (res) *res = r;
   return GRB_SUCCESS;
 }

@@ -26,7 +26,7 @@
 //   appends  are staged per wave in LDS, kKcStage at a time, and reserved with one atomic per flush.
 // The live vertices at the start of level k are the k-core, so the scan that opens the last level has counted the
 // kmax-core.  Working memory: deg and order, 8 bytes per vertex, and 2.25 KiB of state, one allocation.
-#include "persist_common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -46,7 +46,7 @@ struct KcState {                    // zeroed by the host before the launch
   unsigned added[3][32];            // what pass p appended: added[p % 3]; workgroup 0 clears added[(p + 1) % 3] meanwhile
   KcSlot slot[4];                   // scan s adds into slot[s & 3]; workgroup 0 clears slot[(s + 2) & 3] meanwhile
   unsigned long long rec[kKcRec];   // [0] edges x 2 [1] result_edges x 2 [2] kmax [3] levels [4] result_vertices [5] passes
-                                    // [6] done; [8]: kc_compare_kernel's flag
+                                    // [6] done; [8]: the symmetry check's flag (graph_common.hpp)
 };
 constexpr int kKcFlag = 8, kKcDone = 6;
 
@@ -58,45 +58,6 @@ struct KcArgs {
   Index* order;
   KcState* st;
 };
-
-// flag |= 1 when the CSR and the CSC differ (a symmetric structure has the same arrays both ways)
-__global__ __launch_bounds__(kBlock) void kc_compare_kernel(const Index* __restrict__ a_ptr, const Index* __restrict__ b_ptr, long long n1,
-                                                            const Index* __restrict__ a_ind, const Index* __restrict__ b_ind, long long nnz,
-                                                            unsigned int* __restrict__ flag) {
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n1 + nnz; i += (long long)gridDim.x * kBlock)
-    bad |= i < n1 ? a_ptr[i] != b_ptr[i] : a_ind[i - n1] != b_ind[i - n1];
-  if (__ballot(bad) != 0ull && lane_id() == 0) atomicOr(flag, 1u);
-}
-
-// ---- a wave's staged appends ----------------------------------------------------------------------------------------------
-// cnt is the same in every lane; every lane of the wave calls these together
-struct KcOut {
-  Index* buf;                       // the wave's stage (LDS)
-  unsigned cnt;                     // staged
-  unsigned* added;                  // the pass's counter
-  unsigned tail;                    // the queue's length when the pass began
-};
-__device__ __forceinline__ void kc_flush(const KcArgs& a, KcOut& o, int lane) {
-  if (o.cnt == 0u) return;
-  Index* const buf = o.buf;
-  const unsigned cnt = o.cnt;
-  __builtin_amdgcn_wave_barrier();
-  unsigned base = 0;
-  if (lane == 0) base = atomicAdd(o.added, cnt);
-  base = o.tail + (unsigned)__shfl((int)base, 0, kWave);
-  for (unsigned i = (unsigned)lane; i < cnt; i += kWave)
-    if (base + i < (unsigned)a.n) publish(&a.order[base + i], buf[i]);       // (always: a vertex is appended once)
-  __builtin_amdgcn_wave_barrier();
-  o.cnt = 0u;
-}
-__device__ __forceinline__ void kc_push(const KcArgs& a, KcOut& o, int lane, bool want, Index u) {
-  const unsigned long long m = __ballot(want);
-  if (m == 0ull) return;
-  if (o.cnt + kWave > (unsigned)kKcStage) kc_flush(a, o, lane);
-  if (want) o.buf[o.cnt + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = u;
-  o.cnt += (unsigned)__popcll(m);
-}
 
 // ---- removing one end of up to N edges: the loads, then the checks, then the atomics, each stage for all N ---------------
 template <int N>
@@ -122,18 +83,15 @@ __device__ __forceinline__ void kc_hit(const KcArgs& a, const Index (&u)[N], boo
 
 // the row [b, e) walked by kThreads threads (t: this one's number among them); every lane of every wave of them calls it
 template <int kThreads>
-__device__ __forceinline__ void kc_walk(const KcArgs& a, Index b, Index e, int t, int lane, int T, KcOut& o) {
-  // up to three entries before the first 16-byte boundary, whole quads, up to three entries behind them
-  Index b4 = b + (Index)((4u - (unsigned)((reinterpret_cast<uintptr_t>(a.ind + b) >> 2) & 3u)) & 3u);
-  if (b4 > e) b4 = e;
-  const Index nq = (e - b4) >> 2, te = b4 + 4 * nq;
+__device__ __forceinline__ void kc_walk(const KcArgs& a, Index b, Index e, int t, int lane, int T, WaveStage& o) {
+  const QuadSpan s = quad_span(a.ind, b, e);
+  const Index b4 = s.b4, nq = s.nq, te = s.te, nh = s.nh, ns = s.ns;
   if (kThreads == kWave || t < kWave) {
-    const Index nh = b4 - b, ns = nh + (e - te);
     Index u[1] = {0};
     bool ok[1] = {t < ns};
     if (ok[0]) u[0] = a.ind[t < nh ? b + t : te + (t - nh)];
     kc_hit<1>(a, u, ok, T);
-    kc_push(a, o, lane, ok[0], u[0]);
+    stage_push<kKcStage>(o, lane, ok[0], u[0]);
   }
   for (Index q0 = 0; q0 < nq; q0 += kThreads) {
     const Index q = q0 + t;
@@ -143,19 +101,8 @@ __device__ __forceinline__ void kc_walk(const KcArgs& a, Index b, Index e, int t
     const Index u[4] = {c.x, c.y, c.z, c.w};
     kc_hit<4>(a, u, ok, T);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) kc_push(a, o, lane, ok[j], u[j]);
+    for (int j = 0; j < 4; ++j) stage_push<kKcStage>(o, lane, ok[j], u[j]);
   }
-}
-
-__device__ __forceinline__ int kc_degree(const KcArgs& a, Index v) {
-  const Index b = a.ptr[v], e = a.ptr[v + 1];
-  Index lo = b, hi = e;                                  // a stored diagonal (columns ascending)
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a.ind[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  const int d = (int)(e - b) - (lo < e && a.ind[lo] == v ? 1 : 0);
-  return d > 0 ? d : 0;
 }
 
 __global__ __launch_bounds__(kPThreads) void kcore_persistent_kernel(KcArgs a) {
@@ -170,7 +117,7 @@ __global__ __launch_bounds__(kPThreads) void kcore_persistent_kernel(KcArgs a) {
   const long long gwave = (long long)wave * G + blockIdx.x, gwaves = (long long)G * kPWaves;   // neighbouring chunks: different CUs
   KcState* st = a.st;
   if (*reinterpret_cast<const unsigned int*>(&st->rec[kKcFlag]) != 0u) return;   // not symmetric: every workgroup reads the same word
-  KcOut o = {s_stage[wave], 0u, &st->added[0][0], 0u};
+  WaveStage o = {s_stage[wave], 0u, a.order, &st->added[0][0], 0u, (unsigned)a.n};   // base: the queue's length when the pass began
   unsigned gen = 0;
   const bool peel_all = a.k < 0;
   const long long n = a.n;
@@ -181,14 +128,14 @@ __global__ __launch_bounds__(kPThreads) void kcore_persistent_kernel(KcArgs a) {
   unsigned scans = 0, passes = 0, levels = 0;
   // a pass begins: its counter, the next one's cleared; and ends: the barrier, then what it appended
   auto pass_begin = [&]() {
-    o.added = &st->added[passes % 3u][0];
-    o.tail = tail;
+    o.counter = &st->added[passes % 3u][0];
+    o.base = tail;
     if (blockIdx.x == 0 && tid == 0) publish(&st->added[(passes + 1u) % 3u][0], 0u);
   };
   auto pass_end = [&]() -> bool {
-    kc_flush(a, o, lane);
+    stage_flush(o, lane);
     if (!grid_sync(&st->bar, gen, false)) return false;
-    tail += fresh(o.added);
+    tail += fresh(o.counter);
     if (tail > (unsigned)a.n) tail = (unsigned)a.n;
     ++passes;
     return true;
@@ -215,7 +162,7 @@ __global__ __launch_bounds__(kPThreads) void kcore_persistent_kernel(KcArgs a) {
       const bool ok = v < n;
       int d = 0;
       if (ok) {
-        if (first) { d = kc_degree(a, (Index)v); publish(&a.deg[v], d); }
+        if (first) { d = row_degree_no_diag(a.ptr, a.ind, (Index)v); publish(&a.deg[v], d); }
         else d = fresh(&a.deg[v]);
       }
       bool alive = ok && d > kprev;
@@ -229,9 +176,9 @@ __global__ __launch_bounds__(kPThreads) void kcore_persistent_kernel(KcArgs a) {
         ++my_live;
         my_sum += (unsigned long long)d;
       }
-      if (!final_pass) kc_push(a, o, lane, alive && d <= want, (Index)v);
+      if (!final_pass) stage_push<kKcStage>(o, lane, alive && d <= want, (Index)v);
     }
-    kc_flush(a, o, lane);
+    stage_flush(o, lane);
     my_inv = wave_max_u32(my_inv);
     my_live = wave_sum_u32(my_live);
     my_sum = wave_sum_u64(my_sum);
@@ -300,7 +247,7 @@ __global__ __launch_bounds__(kPThreads) void kcore_persistent_kernel(KcArgs a) {
             }
             kc_hit<4>(a, u, ok, T);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) kc_push(a, o, lane, ok[j], u[j]);
+            for (int j = 0; j < 4; ++j) stage_push<kKcStage>(o, lane, ok[j], u[j]);
           }
         }
         unsigned long long mids = __ballot(len > kKcLaneLen && len <= kKcWaveLen);
@@ -349,14 +296,6 @@ __global__ __launch_bounds__(kPThreads) void kcore_persistent_kernel(KcArgs a) {
 
 namespace {
 
-struct KcEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~KcEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 grb_info kcore_empty(grb_vector out, int k, grb_kcore_result* res) {       // n = 0
   GRB_TRY(ctx_init());
   GRB_TRY(grb_vector_set_storage(out, GRB_DENSE));
@@ -372,18 +311,12 @@ grb_info kcore_run(grb_vector out, grb_matrix A, int k, grb_kcore_result* res) {
   Context& c = ctx();
   hipStream_t s = c.stream;
   const Index n = A->nrows;
-  const bool own_csc = !A->csc_alias && A->csc.ptr != nullptr;
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, kcore_persistent_kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
-  }
-  KcEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  GRB_TRY(persistent_kernel_fits(kcore_persistent_kernel));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- one allocation: the state, deg, order
-  const size_t st_bytes = (sizeof(KcState) + 255) & ~(size_t)255;
-  const size_t vw = ((size_t)n + 63) & ~(size_t)63;
+  const size_t st_bytes = pad_bytes(sizeof(KcState));
+  const size_t vw = pad_words((size_t)n);
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, st_bytes + 8 * vw));
   KcArgs a;
@@ -394,18 +327,12 @@ grb_info kcore_run(grb_vector out, grb_matrix A, int k, grb_kcore_result* res) {
   a.st = (KcState*)work.p;
   a.deg = (int*)((char*)work.p + st_bytes);
   a.order = (Index*)(a.deg + vw);
-  // the output's dense storage, before anything runs (allocates only where it has none yet); it stays as it was until the end
-  const int old_type = out->vec_type;
-  const grb_info si = grb_vector_set_storage(out, GRB_DENSE);
-  out->vec_type = old_type;
-  if (si != GRB_SUCCESS || !out->d_val) return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
+  GRB_TRY(dense_out_prepare(out, n));                    // before anything runs; out stays as it was until the end
 
   GRB_TRY(bfs_lanes_fence(s));      // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
   GRB_HIP_TRY(hipEventRecord(ev.a, s));
   GRB_HIP_TRY(hipMemsetAsync(work.p, 0, st_bytes, s));
-  if (own_csc)
-    hipLaunchKernelGGL(kc_compare_kernel, dim3(stream_grid((long long)n + 1 + (long long)A->nvals)), dim3(kBlock), 0, s, A->csr.ptr, A->csc.ptr,
-                       (long long)n + 1, A->csr.ind, A->csc.ind, (long long)A->nvals, (unsigned int*)&a.st->rec[kKcFlag]);
+  launch_symmetry_check<false>(A, (unsigned int*)&a.st->rec[kKcFlag], s);
   hipLaunchKernelGGL(kcore_persistent_kernel, dim3(c.num_cu), dim3(kPThreads), 0, s, a);
   GRB_HIP_TRY(hipGetLastError());
   GRB_HIP_TRY(hipEventRecord(ev.b, s));
@@ -414,10 +341,7 @@ grb_info kcore_run(grb_vector out, grb_matrix A, int k, grb_kcore_result* res) {
   GRB_HIP_TRY(hipStreamSynchronize(s));                  // the call's one read
   if ((unsigned int)h_rec[kKcFlag] != 0u) return GRB_INVALID_VALUE;         // A's CSR and CSC differ: not symmetric
   if (h_rec[kKcDone] != 1ull) return GRB_PANIC;                              // a grid barrier gave up
-  GRB_HIP_TRY(hipMemcpyAsync(out->d_val, a.deg, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-  GRB_HIP_TRY(hipStreamSynchronize(s));
-  out->vec_type = GRB_DENSE;
-  out->d_nnz = n;
+  GRB_TRY(dense_out_commit(out, a.deg, n, s));
   grb_kcore_result r = {};
   r.edges = (int64_t)(h_rec[0] / 2);
   r.result_edges = (int64_t)(h_rec[1] / 2);

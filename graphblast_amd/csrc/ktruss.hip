@@ -26,7 +26,7 @@
 // One round is filter + tasks (+ the support computation on what is left); the host reads {survivors, wave tasks,
 // workgroup tasks} once per round, the round's only synchronisation.  Nothing is allocated inside the loop: three sets of
 // arrays (G's own, never overwritten, and two that alternate) are carved from one allocation up front.
-#include "common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -45,35 +45,15 @@ static_assert(kKtBits / 32 <= kKtWaveSlots && kKtTask == kBlock && kKtWaveLen ==
 
 __device__ __forceinline__ unsigned kt_hash(unsigned x, int slots) { return (x * 0x9E3779B1u) >> (32 - (31 - __builtin_clz(slots))); }
 
-// the first position in [lo, hi) whose column is >= x (hi if none): columns ascend
-__device__ inline Index kt_lower_bound(const Index* __restrict__ ind, Index lo, Index hi, Index x) {
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (ind[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // ---- prepare ------------------------------------------------------------------------------------------------------------
-// flag |= 1 when the two orientations differ in a pointer or an index: A is not symmetric in structure
-__global__ __launch_bounds__(kBlock) void kt_compare_kernel(const Index* __restrict__ a_ptr, const Index* __restrict__ b_ptr, long long n1,
-                                                            const Index* __restrict__ a_ind, const Index* __restrict__ b_ind, long long nnz,
-                                                            unsigned int* __restrict__ flag) {
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n1 + nnz; i += (long long)gridDim.x * kBlock)
-    bad |= i < n1 ? a_ptr[i] != b_ptr[i] : a_ind[i - n1] != b_ind[i - n1];
-  if (__ballot(bad) != 0ull && lane_id() == 0) atomicOr(flag, 1u);
-}
-
 // where the diagonal lies in row r: dlo[r] its first position, cnt[r] how many entries hold it (0 or 1; cnt[n] = 0)
 __global__ __launch_bounds__(kBlock) void kt_diag_kernel(const Index* __restrict__ ptr, const Index* __restrict__ ind, Index n,
                                                          Index* __restrict__ dlo, unsigned int* __restrict__ cnt) {
   const long long r = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (r > n) return;
   if (r == n) { cnt[n] = 0u; return; }
-  const Index a = kt_lower_bound(ind, ptr[r], ptr[r + 1], (Index)r);
-  const Index b = kt_lower_bound(ind, a, ptr[r + 1], (Index)r + 1);
+  const Index a = index_lower_bound(ind, ptr[r], ptr[r + 1], (Index)r);
+  const Index b = index_lower_bound(ind, a, ptr[r + 1], (Index)r + 1);
   dlo[r] = a;
   cnt[r] = (unsigned int)(b - a);
 }
@@ -104,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void kt_prepare_kernel(const Index* __restr
       // the entry becomes its own twin, nothing is read out of bounds, and the call fails on the flag
       Index t = -1;
       if (j >= 0 && j < n) {
-        t = kt_lower_bound(ind, ptr[j], ptr[j + 1], (Index)r);
+        t = index_lower_bound(ind, ptr[j], ptr[j + 1], (Index)r);
         if (t >= ptr[j + 1] || ind[t] != (Index)r) t = -1;
       }
       if (t < 0) atomicOr(flag, 1u);
@@ -361,16 +341,6 @@ __global__ __launch_bounds__(kBlock) void kt_values_kernel(const int* __restrict
 namespace {
 
 inline int kt_grid(long long items) { return (int)((items + kBlock - 1) / kBlock > 0 ? (items + kBlock - 1) / kBlock : 1); }
-inline size_t kt_pad(size_t words) { return (words + 63) & ~(size_t)63; }   // every array begins on a 256-byte line
-
-struct KtEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~KtEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 // C = the k-truss of A's graph with its supports (trussness false), or G with every edge's trussness (true)
 grb_info truss_run(grb_matrix C, grb_matrix A, int k_in, bool trussness, grb_truss_result* res) {
   hipStream_t s = ctx().stream;
@@ -378,21 +348,18 @@ grb_info truss_run(grb_matrix C, grb_matrix A, int k_in, bool trussness, grb_tru
   const long long nnz = A->csr.nvals;
   grb_truss_result out = {};
   out.kmax = trussness ? 2 : k_in;
-  KtEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- prepare: the symmetry check and the diagonal, one read
   EwmBuf pre;
   const size_t scan_words = device_scan_u32_scratch(2 * (long long)n + 1) / 4 + 1;
-  GRB_TRY(ewm_alloc(&pre, 4 * (kt_pad((size_t)n + 1) * 2 + kt_pad(scan_words) + 64)));
+  GRB_TRY(ewm_alloc(&pre, 4 * (pad_words((size_t)n + 1) * 2 + pad_words(scan_words) + 64)));
   unsigned int* d_info = (unsigned int*)pre.p;           // [0] survivors [1] wave tasks [2] workgroup tasks [3] asymmetric
   Index* d_dlo = (Index*)(d_info + 64);
-  unsigned int* d_off = (unsigned int*)(d_dlo + kt_pad((size_t)n + 1));
-  unsigned int* d_scan = d_off + kt_pad((size_t)n + 1);
+  unsigned int* d_off = (unsigned int*)(d_dlo + pad_words((size_t)n + 1));
+  unsigned int* d_scan = d_off + pad_words((size_t)n + 1);
   GRB_HIP_TRY(hipMemsetAsync(d_info, 0, 256, s));
-  if (!A->csc_alias)
-    hipLaunchKernelGGL(kt_compare_kernel, dim3(stream_grid((long long)n + 1 + nnz)), dim3(kBlock), 0, s, A->csr.ptr, A->csc.ptr,
-                       (long long)n + 1, A->csr.ind, A->csc.ind, nnz, d_info + 3);
+  launch_symmetry_check<false>(A, d_info + 3, s);
   hipLaunchKernelGGL(kt_diag_kernel, dim3(kt_grid((long long)n + 1)), dim3(kBlock), 0, s, A->csr.ptr, A->csr.ind, n, d_dlo, d_off);
   GRB_HIP_TRY(hipGetLastError());
   GRB_TRY(device_exclusive_scan_u32_async(d_off, (long long)n + 1, d_scan));
@@ -405,14 +372,14 @@ grb_info truss_run(grb_matrix C, grb_matrix A, int k_in, bool trussness, grb_tru
   const long long E0 = nnz - (long long)ndiag;
   out.edges = E0 / 2;
   // ---- the three sets, the positions, the trussness and the task lists: one allocation
-  const size_t ew = kt_pad((size_t)E0 + 4), pw = kt_pad((size_t)n + 1);
+  const size_t ew = pad_words((size_t)E0 + 4), pw = pad_words((size_t)n + 1);
   const size_t max_wave_tasks = (size_t)n, max_block_tasks = (size_t)(E0 / kKtTask + E0 / (kKtWaveLen + 1) + 1);
   const int max_tiles = (int)((E0 + kKtTile - 1) / kKtTile);
-  const size_t tile_words = kt_pad((size_t)max_tiles + 1 + device_scan_u32_scratch((long long)max_tiles + 1) / 4 + 1);
-  const size_t cnt_words = kt_pad(2 * (size_t)n + 1);
+  const size_t tile_words = pad_words((size_t)max_tiles + 1 + device_scan_u32_scratch((long long)max_tiles + 1) / 4 + 1);
+  const size_t cnt_words = pad_words(2 * (size_t)n + 1);
   EwmBuf work;
-  GRB_TRY(ewm_alloc(&work, 4 * (3 * (pw + 4 * ew) + 2 * ew + tile_words + cnt_words + 2 * kt_pad(max_wave_tasks + 1) +
-                                2 * kt_pad(max_block_tasks + 1))));
+  GRB_TRY(ewm_alloc(&work, 4 * (3 * (pw + 4 * ew) + 2 * ew + tile_words + cnt_words + 2 * pad_words(max_wave_tasks + 1) +
+                                2 * pad_words(max_block_tasks + 1))));
   KtSet set[3];
   Index* q = (Index*)work.p;
   for (int i = 0; i < 3; ++i) {
@@ -426,7 +393,7 @@ grb_info truss_run(grb_matrix C, grb_matrix A, int k_in, bool trussness, grb_tru
   int* d_truss = (int*)q; q += ew;
   unsigned int* d_tiles = (unsigned int*)q; q += tile_words;
   unsigned int* d_cnt = (unsigned int*)q; q += cnt_words;
-  int2* d_wave_tasks = (int2*)q; q += 2 * kt_pad(max_wave_tasks + 1);
+  int2* d_wave_tasks = (int2*)q; q += 2 * pad_words(max_wave_tasks + 1);
   int2* d_block_tasks = (int2*)q;
   auto build_tasks = [&](const KtSet& g) -> grb_info {
     hipLaunchKernelGGL(kt_task_count_kernel, dim3(kt_grid((long long)n + 1)), dim3(kBlock), 0, s, g.ptr, n, d_cnt);

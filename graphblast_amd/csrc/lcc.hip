@@ -26,7 +26,7 @@
 //            atomic per triangle, no floating-point atomic: integer adds commute, so the bits do not depend on the order.
 //   final    d (d - 1), the f64 quotient rounded to f32 once, and the record's totals.
 // Everything is carved from one allocation before the first kernel; the host reads one record.
-#include "common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -43,24 +43,6 @@ constexpr int kLcChunk[2] = {256, 1024};                 // partners per task, b
 constexpr int kLcTotals = 64;                            // partial triangle counts (one address would serialise the tasks)
 static_assert((kLcWaveSlots & (kLcWaveSlots - 1)) == 0 && (kLcSlots & (kLcSlots - 1)) == 0 && kLcTotals == kWave, "sizes");
 
-__device__ __forceinline__ Index lc_lower_bound(const Index* __restrict__ a, Index lo, Index hi, Index x) {
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// flag |= 1 when the CSR and the CSC differ (a symmetric structure has the same arrays both ways)
-__global__ __launch_bounds__(kBlock) void lc_compare_kernel(const Index* __restrict__ a_ptr, const Index* __restrict__ b_ptr, long long n1,
-                                                            const Index* __restrict__ a_ind, const Index* __restrict__ b_ind, long long nnz,
-                                                            unsigned int* __restrict__ flag) {
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n1 + nnz; i += (long long)gridDim.x * kBlock)
-    bad |= i < n1 ? a_ptr[i] != b_ptr[i] : a_ind[i - n1] != b_ind[i - n1];
-  if (__ballot(bad) != 0ull && lane_id() == 0) atomicOr(flag, 1u);
-}
-
 // ---- S: the merged rows ---------------------------------------------------------------------------------------------------
 // kFill false: sptr[v] = d(v).  kFill true: sptr is scanned and row v of S is written.  cptr == nullptr: rows only, m = 2.
 // An entry's place in the merged row = the kept entries of its own list before it + the kept entries of the other list
@@ -74,9 +56,9 @@ __global__ __launch_bounds__(kBlock) void lc_merge_kernel(const Index* __restric
   for (long long v = (long long)blockIdx.x * kWavesPerBlock + wave_id(); v < n; v += (long long)gridDim.x * kWavesPerBlock) {
     const Index rb = rptr[v], re = rptr[v + 1];
     const Index cb = cptr ? cptr[v] : 0, ce = cptr ? cptr[v + 1] : 0;
-    const Index dr = lc_lower_bound(rind, rb, re, (Index)v);             // where the diagonal lies, if stored
+    const Index dr = index_lower_bound(rind, rb, re, (Index)v);             // where the diagonal lies, if stored
     const bool has_r = dr < re && rind[dr] == (Index)v;
-    const Index dc = cptr ? lc_lower_bound(cind, cb, ce, (Index)v) : 0;
+    const Index dc = cptr ? index_lower_bound(cind, cb, ce, (Index)v) : 0;
     const bool has_c = cptr && dc < ce && cind[dc] == (Index)v;
     const unsigned base = kFill ? sptr[v] : 0u, room = kFill ? sptr[v + 1] - base : 0u;
     unsigned both = 0;                                                   // entries in both lists, before this step
@@ -87,7 +69,7 @@ __global__ __launch_bounds__(kBlock) void lc_merge_kernel(const Index* __restric
       Index pc = cb;
       bool found = false;
       if (keep && cptr) {
-        pc = lc_lower_bound(cind, cb, ce, u);
+        pc = index_lower_bound(cind, cb, ce, u);
         found = pc < ce && cind[pc] == u;
       }
       const unsigned long long bm = __ballot(found);
@@ -107,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void lc_merge_kernel(const Index* __restric
       Index pr = rb;
       bool found = false;
       if (keep) {
-        pr = lc_lower_bound(rind, rb, re, w);
+        pr = index_lower_bound(rind, rb, re, w);
         found = pr < re && rind[pr] == w;
       }
       const unsigned long long bm = __ballot(found);
@@ -347,7 +329,7 @@ __global__ __launch_bounds__(kThreads) void lc_enum_kernel(LcLists a, const int4
 }
 
 // ---- the quotient and the record ------------------------------------------------------------------------------------------
-// rec: [0] closed [1] wedges [2] the sum of d [3] max d [4] triangles ([5]: lc_compare_kernel's flag)
+// rec: [0] closed [1] wedges [2] the sum of d [3] max d [4] triangles ([5]: the symmetry check's flag, graph_common.hpp)
 __global__ __launch_bounds__(kBlock) void lc_final_kernel(const unsigned int* __restrict__ sptr, const unsigned long long* __restrict__ num,
                                                           const unsigned long long* __restrict__ tot, Index n, float* __restrict__ out,
                                                           unsigned long long* __restrict__ rec) {
@@ -391,16 +373,6 @@ __global__ __launch_bounds__(kBlock) void lc_final_kernel(const unsigned int* __
 
 namespace {
 
-struct LcEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~LcEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
-inline size_t lc_pad(size_t words) { return (words + 63) & ~(size_t)63; }   // every array begins on a 256-byte line
-
 grb_info lcc_zero(grb_vector lcc, grb_lcc_result* res) {
   GRB_TRY(ctx_init());
   GRB_TRY(grb_vector_set_storage(lcc, GRB_DENSE));
@@ -419,20 +391,18 @@ grb_info lcc_run(grb_vector lcc, grb_matrix A, bool directed, grb_lcc_result* re
   hipStream_t s = ctx().stream;
   const Index n = A->nrows;
   const size_t nnz = (size_t)A->nvals;
-  const bool own_csc = !A->csc_alias && A->csc.ptr != nullptr;
   const size_t smax = directed ? 2 * nnz : nnz;          // S's entries at most; O's and P's are no more
   // (positions are 32-bit: O's with up to three fillings a list)
   if ((unsigned long long)smax + 4ull * (unsigned long long)n >= 0xfffffff0ull) return GRB_OUT_OF_MEMORY;
-  LcEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- one allocation: the record, seven arrays of n + 1 words, the scan's totals, num, the values, S, O, P, the tasks
-  const size_t vw = lc_pad((size_t)n + 2), recw = lc_pad(16 + 2 * kLcTotals);
-  const size_t scanw = lc_pad(device_scan_u32_scratch((long long)n + 1) / 4 + 1);
-  const size_t sw = lc_pad(smax + 4), ow = lc_pad(smax + 4 * (size_t)n + 8);
+  const size_t vw = pad_words((size_t)n + 2), recw = pad_words(16 + 2 * kLcTotals);
+  const size_t scanw = pad_words(device_scan_u32_scratch((long long)n + 1) / 4 + 1);
+  const size_t sw = pad_words(smax + 4), ow = pad_words(smax + 4 * (size_t)n + 8);
   const size_t room0 = (size_t)n + smax / kLcChunk[0] + 2, room1 = (size_t)n + smax / kLcChunk[1] + 2;
   EwmBuf work;
-  GRB_TRY(ewm_alloc(&work, 4 * (recw + 7 * vw + scanw + 2 * vw + vw + sw + ow + sw + 4 * lc_pad(room0) + 4 * lc_pad(room1))));
+  GRB_TRY(ewm_alloc(&work, 4 * (recw + 7 * vw + scanw + 2 * vw + vw + sw + ow + sw + 4 * pad_words(room0) + 4 * pad_words(room1))));
   unsigned int* q = (unsigned int*)work.p;
   unsigned long long* d_rec = (unsigned long long*)q;                    // [0..7] the record, then kLcTotals partial counts
   unsigned long long* d_tot = d_rec + 8;
@@ -450,13 +420,9 @@ grb_info lcc_run(grb_vector lcc, grb_matrix A, bool directed, grb_lcc_result* re
   unsigned int* d_S = q; q += sw;
   unsigned int* d_O = q; q += ow;
   unsigned int* d_P = q; q += sw;
-  int4* d_t0 = (int4*)q; q += 4 * lc_pad(room0);
+  int4* d_t0 = (int4*)q; q += 4 * pad_words(room0);
   int4* d_t1 = (int4*)q;
-  // lcc's dense storage, before anything runs (allocates only where lcc has none yet); lcc stays as it was until the end
-  const int old_type = lcc->vec_type;
-  const grb_info si = grb_vector_set_storage(lcc, GRB_DENSE);
-  lcc->vec_type = old_type;
-  if (si != GRB_SUCCESS || !lcc->d_val) return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
+  GRB_TRY(dense_out_prepare(lcc, n));                    // before anything runs; lcc stays as it was until the end
 
   GRB_HIP_TRY(hipEventRecord(ev.a, s));
   GRB_HIP_TRY(hipMemsetAsync(work.p, 0, 4 * (recw + 7 * vw + scanw + 2 * vw), s));   // the record, the counts, num
@@ -464,9 +430,7 @@ grb_info lcc_run(grb_vector lcc, grb_matrix A, bool directed, grb_lcc_result* re
   const Index* rind = A->csr.ind;
   const Index* cptr = directed ? A->csc.ptr : nullptr;
   const Index* cind = directed ? A->csc.ind : nullptr;
-  if (!directed && own_csc)
-    hipLaunchKernelGGL(lc_compare_kernel, dim3(stream_grid((long long)n + 1 + (long long)nnz)), dim3(kBlock), 0, s, A->csr.ptr, A->csc.ptr,
-                       (long long)n + 1, A->csr.ind, A->csc.ind, (long long)nnz, (unsigned int*)(d_rec + 5));
+  if (!directed) launch_symmetry_check<false>(A, (unsigned int*)(d_rec + 5), s);
   const int wgrid = stream_grid(n, kWavesPerBlock), vgrid = (int)(((long long)n + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(lc_merge_kernel<false>, dim3(wgrid), dim3(kBlock), 0, s, rptr, rind, cptr, cind, n, d_sptr, d_S);
   GRB_HIP_TRY(hipGetLastError());
@@ -503,10 +467,7 @@ grb_info lcc_run(grb_vector lcc, grb_matrix A, bool directed, grb_lcc_result* re
   GRB_HIP_TRY(hipMemcpyAsync(h_rec, d_rec, sizeof(h_rec), hipMemcpyDeviceToHost, s));
   GRB_HIP_TRY(hipStreamSynchronize(s));                  // the call's one read
   if ((unsigned int)h_rec[5] != 0u) return GRB_INVALID_VALUE;            // A's CSR and CSC differ: not symmetric
-  GRB_HIP_TRY(hipMemcpyAsync(lcc->d_val, d_out, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-  GRB_HIP_TRY(hipStreamSynchronize(s));
-  lcc->vec_type = GRB_DENSE;
-  lcc->d_nnz = n;
+  GRB_TRY(dense_out_commit(lcc, d_out, n, s));
   grb_lcc_result out = {};
   out.closed = (int64_t)h_rec[0];
   out.wedges = (int64_t)h_rec[1];

@@ -27,7 +27,7 @@
 // bits at cpos of the smaller end.  The weight is a two-level sum over the vertices with mate(v) > v whose shape depends on
 // n alone.  Working memory: 24 bytes per vertex and about 3 KiB (the state, the scan's totals, the partial sums), one
 // allocation.
-#include "persist_common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -50,7 +50,7 @@ struct MtState {                    // zeroed by the host before the launch
   MtSlot slot[4];                   // pass p adds into slot[p & 3]; workgroup 0 clears slot[(p + 2) & 3] meanwhile
   unsigned queued[2][32];           // round r evaluates queued[r & 1][0] vertices; its pass C counts the next round's in the other
   unsigned matched[32];             // vertices in the list so far (only pass B adds)
-  unsigned flag[32];                // mt_compare_kernel: 1 = the CSR and the CSC differ
+  unsigned flag[32];                // the symmetry check (graph_common.hpp): 1 = the CSR and the CSC differ
   unsigned long long rec[kMtRec];   // [0] off-diagonal entries [1] matched vertices [2] isolated [3] rounds [4] passes
                                     // [5] evaluations [6] done [7] a NaN off the diagonal
 };
@@ -67,13 +67,6 @@ struct MtArgs {
   MtState* st;
 };
 
-// the monotone map of a weight's bits to an unsigned: f32 by value with -0 = +0, i32 as a signed integer (as in msf.hip)
-__device__ __forceinline__ unsigned mt_canon(unsigned b, int f32) { return f32 && b == 0x80000000u ? 0u : b; }
-__device__ __forceinline__ unsigned mt_order(unsigned b, int f32) {
-  if (!f32) return b ^ 0x80000000u;
-  b = mt_canon(b, 1);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 __device__ __forceinline__ unsigned mt_mix(unsigned x) {
   x ^= x >> 16;
   x *= 0x85ebca6bu;
@@ -88,50 +81,8 @@ __device__ __forceinline__ unsigned mt_prio(const MtArgs& a, Index v, Index u, u
     const unsigned lo = (unsigned)(u < v ? u : v), hi = (unsigned)(u < v ? v : u);
     return mt_mix(mt_mix(lo + a.seed) ^ hi);
   }
-  const unsigned o = mt_order(w, a.f32);
+  const unsigned o = weight_order(w, a.f32);
   return a.mode == GRB_MATCH_HEAVIEST ? ~o : o;
-}
-
-// flag |= 1 when the CSR and the CSC differ: pointers, indices and, with `values`, values as bits with -0 taken as +0
-__global__ __launch_bounds__(kBlock) void mt_compare_kernel(const Index* __restrict__ a_ptr, const Index* __restrict__ b_ptr, long long n1,
-                                                            const Index* __restrict__ a_ind, const Index* __restrict__ b_ind,
-                                                            const unsigned* __restrict__ a_val, const unsigned* __restrict__ b_val, long long nnz,
-                                                            int f32, int values, unsigned int* __restrict__ flag) {
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n1 + nnz; i += (long long)gridDim.x * kBlock) {
-    if (i < n1) bad |= a_ptr[i] != b_ptr[i];
-    else bad |= a_ind[i - n1] != b_ind[i - n1] || (values && mt_canon(a_val[i - n1], f32) != mt_canon(b_val[i - n1], f32));
-  }
-  if (__ballot(bad) != 0ull && lane_id() == 0) atomicOr(flag, 1u);
-}
-
-// ---- a wave's staged appends of vertices ----------------------------------------------------------------------------------
-// cnt is the same in every lane; every lane of the wave calls these together
-struct MtOut {
-  Index* sv;                        // the wave's stage (LDS)
-  unsigned cnt;                     // staged
-  Index* dst;                       // the list the wave appends to, its counter, its room
-  unsigned* counter;
-  unsigned cap;
-};
-__device__ __forceinline__ void mt_flush(MtOut& o, int lane) {
-  if (o.cnt == 0u) return;
-  const unsigned cnt = o.cnt;
-  __builtin_amdgcn_wave_barrier();
-  unsigned at = 0;
-  if (lane == 0) at = atomicAdd(o.counter, cnt);
-  at = (unsigned)__shfl((int)at, 0, kWave);
-  for (unsigned i = (unsigned)lane; i < cnt; i += kWave)
-    if (at + i < o.cap) publish(&o.dst[at + i], o.sv[i]);                    // (always on a symmetric input: a vertex enters once)
-  __builtin_amdgcn_wave_barrier();
-  o.cnt = 0u;
-}
-__device__ __forceinline__ void mt_push(MtOut& o, int lane, bool want, Index v) {
-  const unsigned long long m = __ballot(want);
-  if (m == 0ull) return;
-  if (o.cnt + kWave > (unsigned)kMtStage) mt_flush(o, lane);
-  if (want) o.sv[o.cnt + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = v;
-  o.cnt += (unsigned)__popcll(m);
 }
 
 // ---- what a pass does with the entries of a row -----------------------------------------------------------------------------
@@ -177,7 +128,7 @@ struct MtBest {
 struct MtWake {
   static constexpr bool kBest = false;
   const MtArgs& a;
-  MtOut& o;
+  WaveStage& o;
   int lane;
   __device__ __forceinline__ bool wanted(Index) const { return true; }
   template <int N>
@@ -195,7 +146,7 @@ struct MtWake {
       cu[j] = ok[j] ? fresh(&a.cand[u[j]]) : kMtFin;
     }
 #pragma unroll
-    for (int j = 0; j < N; ++j) mt_push(o, lane, ok[j] && cu[j] == v, u[j]);  // (every lane of the wave is here)
+    for (int j = 0; j < N; ++j) stage_push<kMtStage>(o, lane, ok[j] && cu[j] == v, u[j]);  // (every lane of the wave is here)
   }
   __device__ __forceinline__ void settle(Index, unsigned long long, Index) {}
 };
@@ -203,12 +154,9 @@ struct MtWake {
 // the row [b, e) of v walked by kThreads threads (t: this one's number among them); whole waves call it together
 template <int kThreads, typename Op>
 __device__ __forceinline__ void mt_walk(Op& op, const Index* ind, Index v, Index b, Index e, int t, unsigned long long& best, Index& bpos) {
-  // up to three entries before the first 16-byte boundary, whole quads, up to three entries behind them
-  Index b4 = b + (Index)((4u - (unsigned)((reinterpret_cast<uintptr_t>(ind + b) >> 2) & 3u)) & 3u);
-  if (b4 > e) b4 = e;
-  const Index nq = (e - b4) >> 2, te = b4 + 4 * nq;
+  const QuadSpan s = quad_span(ind, b, e);
+  const Index b4 = s.b4, nq = s.nq, te = s.te, nh = s.nh, ns = s.ns;
   if (kThreads == kWave || t < kWave) {
-    const Index nh = b4 - b, ns = nh + (e - te);
     Index u[1] = {0}, p[1] = {0};
     bool ok[1] = {t < ns};
     if (ok[0]) {
@@ -317,18 +265,6 @@ __device__ __forceinline__ void mt_rows(const MtArgs& a, Op& op, long long count
   }
 }
 
-// the length of v's row without a stored diagonal (indices ascending)
-__device__ __forceinline__ int mt_degree(const MtArgs& a, Index v) {
-  const Index b = a.ptr[v], e = a.ptr[v + 1];
-  Index lo = b, hi = e;
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a.ind[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  const int d = (int)(e - b) - (lo < e && a.ind[lo] == v ? 1 : 0);
-  return d > 0 ? d : 0;
-}
-
 __global__ __launch_bounds__(kPThreads) void matching_persistent_kernel(MtArgs a) {
   __shared__ Index s_stage[kPWaves][kMtStage];
   __shared__ MtLds s_rows;
@@ -384,7 +320,7 @@ __global__ __launch_bounds__(kPThreads) void matching_persistent_kernel(MtArgs a
     unsigned long long my_sum = 0;
     pass_begin();
     for (long long v = gtid; v < n; v += gthreads) {
-      const int d = mt_degree(a, (Index)v);
+      const int d = row_degree_no_diag(a.ptr, a.ind, (Index)v);
       publish(&a.mate[v], (int)kMtFree);
       publish(&a.cand[v], d == 0 ? kMtFin : kMtFree);
       publish(&a.cpos[v], (Index)0);
@@ -414,7 +350,7 @@ __global__ __launch_bounds__(kPThreads) void matching_persistent_kernel(MtArgs a
     }
     // ---- B: the pairs that chose each other
     {
-      MtOut o = {s_stage[wave], 0u, a.list, &st->matched[0], (unsigned)a.n};
+      WaveStage o = {s_stage[wave], 0u, a.list, &st->matched[0], 0u, (unsigned)a.n};
       pass_begin();
       if (blockIdx.x == 0 && tid == 0) publish(&st->queued[rounds & 1u][0], 0u);   // (read by everybody before pass A; next added to in the next round's pass C)
       for (long long base = 0; base < count; base += gthreads) {
@@ -433,10 +369,10 @@ __global__ __launch_bounds__(kPThreads) void matching_persistent_kernel(MtArgs a
             }
           }
         }
-        mt_push(o, lane, pv, v);
-        mt_push(o, lane, pu, u);
+        stage_push<kMtStage>(o, lane, pv, v);
+        stage_push<kMtStage>(o, lane, pu, u);
       }
-      mt_flush(o, lane);
+      stage_flush(o, lane);
       if (!pass_end()) return;
     }
     ++rounds;
@@ -447,11 +383,11 @@ __global__ __launch_bounds__(kPThreads) void matching_persistent_kernel(MtArgs a
     if (total == before) break;                          // a round that matched nothing: the last
     // ---- C: the neighbours that lost their candidate
     {
-      MtOut o = {s_stage[wave], 0u, a.queue, &st->queued[rounds & 1u][0], (unsigned)a.n};
+      WaveStage o = {s_stage[wave], 0u, a.queue, &st->queued[rounds & 1u][0], 0u, (unsigned)a.n};
       MtWake op = {a, o, lane};
       pass_begin();
       mt_rows(a, op, (long long)(total - before), a.list + before, s_rows, tid, lane, wave, gwave, gwaves);
-      mt_flush(o, lane);
+      stage_flush(o, lane);
       if (!pass_end()) return;
     }
     unsigned next = fresh(&st->queued[rounds & 1u][0]);
@@ -493,12 +429,10 @@ __global__ __launch_bounds__(kBlock) void mt_fill_kernel(const int* __restrict__
 }
 
 // the weight over the vertices with mate(v) > v, each edge once: block b adds the vertices b * kBlock + t + k * blocks * kBlock in
-// the order of k, its threads' sums by a fixed butterfly, and the last kernel adds the blocks' sums in order.  kF32: f64 sums;
-// else exact 64-bit integer sums.
+// the order of k; the rest of the sum is graph_common.hpp's fixed-order tail (weight_block_sum, weight_final_kernel)
 template <bool kF32>
 __global__ __launch_bounds__(kBlock) void mt_weight_kernel(const int* __restrict__ mate, const Index* __restrict__ cpos, const unsigned* __restrict__ val,
                                                            long long n, unsigned long long* __restrict__ partial) {
-  __shared__ unsigned long long s_part[kWavesPerBlock];
   double fs = 0.0;
   long long is = 0;
   for (long long v = (long long)blockIdx.x * kBlock + threadIdx.x; v < n; v += (long long)gridDim.x * kBlock) {
@@ -509,51 +443,10 @@ __global__ __launch_bounds__(kBlock) void mt_weight_kernel(const int* __restrict
       else is += (long long)(int)w;
     }
   }
-  for (int s = kWave / 2; s > 0; s >>= 1) {
-    if (kF32) fs += __shfl_xor(fs, s, kWave);
-    else is += __shfl_xor(is, s, kWave);
-  }
-  if (lane_id() == 0) s_part[wave_id()] = kF32 ? (unsigned long long)__double_as_longlong(fs) : (unsigned long long)is;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWavesPerBlock; ++w) {
-      if (kF32) fs += __longlong_as_double((long long)s_part[w]);
-      else is += (long long)s_part[w];
-    }
-    partial[blockIdx.x] = kF32 ? (unsigned long long)__double_as_longlong(fs) : (unsigned long long)is;
-  }
-}
-template <bool kF32>
-__global__ void mt_weight_final_kernel(const unsigned long long* __restrict__ partial, int blocks, double* __restrict__ out) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double fs = 0.0;
-  long long is = 0;
-  for (int b = 0; b < blocks; ++b) {
-    if (kF32) fs += __longlong_as_double((long long)partial[b]);
-    else is += (long long)partial[b];
-  }
-  *out = kF32 ? fs : (double)is;
+  weight_block_sum<kF32>(fs, is, partial);
 }
 
 namespace {
-
-struct MtEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~MtEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
-// C's arrays for m entries, exactly
-grb_info mt_side(Side* sd, Index n, long long m) {
-  GRB_TRY(ewm_alloc(&sd->ptr, 4 * ((size_t)n + 1)));
-  GRB_TRY(ewm_alloc(&sd->ind, 4 * (size_t)(m > 0 ? m : 1)));
-  GRB_TRY(ewm_alloc(&sd->val, 4 * (size_t)(m > 0 ? m : 1)));
-  sd->nnz = (Index)m;
-  sd->h_ptr.assign((size_t)n + 1, 0);
-  return GRB_SUCCESS;
-}
 
 grb_info matching_run(grb_vector mate, grb_matrix C, grb_matrix A, int mode, unsigned seed, grb_matching_result* res) {
   GRB_TRY(ctx_init());
@@ -561,25 +454,17 @@ grb_info matching_run(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uns
   hipStream_t s = c.stream;
   const Index n = A->nrows;
   const int f32 = A->dtype == GRB_F32 ? 1 : 0;
-  const bool own_csc = !A->csc_alias && A->csc.ptr != nullptr;
   const bool both = C && C->format != 1;
   grb_matching_result r = {};
   Side sr, sc;
-  if (n > 0) {
-    static int max_per_cu = 0;
-    if (!max_per_cu) {
-      GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, matching_persistent_kernel, kPThreads, 0));
-      if (max_per_cu < 1) return GRB_PANIC;
-    }
-  }
-  MtEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  if (n > 0) GRB_TRY(persistent_kernel_fits(matching_persistent_kernel));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- one allocation: the state, six words per vertex (mate, cand, cpos, queue, list, the flags of the scan), the scan's
   // totals, the partial sums and the weight
-  const size_t st_bytes = (sizeof(MtState) + 255) & ~(size_t)255;
-  const size_t vw = ((size_t)n + 1 + 63) & ~(size_t)63;
-  const size_t scan_bytes = (device_scan_u32_scratch((long long)n + 1) + 63) & ~(size_t)63;
+  const size_t st_bytes = pad_bytes(sizeof(MtState));
+  const size_t vw = pad_words((size_t)n + 1);
+  const size_t scan_bytes = (device_scan_u32_scratch((long long)n + 1) + 63) & ~(size_t)63;   // (to 64 bytes: d_partial is 8-byte words)
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, st_bytes + 24 * vw + scan_bytes + 8 * (size_t)kMtSumBlocks + 64));
   MtArgs a;
@@ -600,22 +485,14 @@ grb_info matching_run(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uns
   unsigned* d_totals = d_flags + vw;
   unsigned long long* d_partial = (unsigned long long*)((char*)d_totals + scan_bytes);   // [kMtSumBlocks]
   double* d_weight = (double*)(d_partial + kMtSumBlocks);
-  // mate's dense storage, before anything runs (allocates only where it has none yet); it stays as it was until the end
-  {
-    const int old_type = mate->vec_type;
-    const grb_info si = grb_vector_set_storage(mate, GRB_DENSE);
-    mate->vec_type = old_type;
-    if (si != GRB_SUCCESS || (n > 0 && !mate->d_val)) return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
-  }
+  GRB_TRY(dense_out_prepare(mate, n));                   // before anything runs; mate stays as it was until the end
   long long M = 0;                                       // matched vertices = C's entries
   if (n > 0) {
     GRB_TRY(bfs_lanes_fence(s));    // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
     GRB_HIP_TRY(hipEventRecord(ev.a, s));
     GRB_HIP_TRY(hipMemsetAsync(work.p, 0, st_bytes, s));
-    if (own_csc)
-      hipLaunchKernelGGL(mt_compare_kernel, dim3(stream_grid((long long)n + 1 + (long long)A->nvals)), dim3(kBlock), 0, s, A->csr.ptr, A->csc.ptr,
-                         (long long)n + 1, A->csr.ind, A->csc.ind, (const unsigned*)A->csr.val, (const unsigned*)A->csc.val,
-                         (long long)A->nvals, f32, mode != GRB_MATCH_HASHED ? 1 : 0, &a.st->flag[0]);
+    if (mode != GRB_MATCH_HASHED) launch_symmetry_check<true>(A, &a.st->flag[0], s);
+    else launch_symmetry_check<false>(A, &a.st->flag[0], s);                  // (a hashed priority never reads the values)
     hipLaunchKernelGGL(matching_persistent_kernel, dim3(c.num_cu), dim3(kPThreads), 0, s, a);
     GRB_HIP_TRY(hipGetLastError());
     struct { unsigned flag[32]; unsigned long long rec[kMtRec]; } h;
@@ -637,17 +514,17 @@ grb_info matching_run(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uns
   }
   // ---- C's arrays
   if (C) {
-    GRB_TRY(mt_side(&sr, n, M));
-    if (both) GRB_TRY(mt_side(&sc, n, M));
+    GRB_TRY(side_alloc(&sr, n, M));
+    if (both) GRB_TRY(side_alloc(&sc, n, M));
   }
   if (M > 0) {
     const int blocks = (int)(((long long)n + kBlock - 1) / kBlock < kMtSumBlocks ? ((long long)n + kBlock - 1) / kBlock : kMtSumBlocks);
     if (f32) {
       hipLaunchKernelGGL(mt_weight_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, a.mate, a.cpos, a.val, (long long)n, d_partial);
-      hipLaunchKernelGGL(mt_weight_final_kernel<true>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
+      hipLaunchKernelGGL(weight_final_kernel<true>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
     } else {
       hipLaunchKernelGGL(mt_weight_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, a.mate, a.cpos, a.val, (long long)n, d_partial);
-      hipLaunchKernelGGL(mt_weight_final_kernel<false>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
+      hipLaunchKernelGGL(weight_final_kernel<false>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
     }
     GRB_HIP_TRY(hipGetLastError());
     GRB_HIP_TRY(hipMemcpyAsync(&r.weight, d_weight, 8, hipMemcpyDeviceToHost, s));
@@ -661,11 +538,7 @@ grb_info matching_run(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uns
                        (const Index*)sr.ptr.p, (Index*)sr.ind.p, (unsigned*)sr.val.p);
     GRB_HIP_TRY(hipGetLastError());
     GRB_HIP_TRY(hipMemcpyAsync(sr.h_ptr.data(), sr.ptr.p, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost, s));
-    if (both) {                                          // the structure is symmetric and so are the values: the CSC is a copy
-      GRB_HIP_TRY(hipMemcpyAsync(sc.ptr.p, sr.ptr.p, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
-      GRB_HIP_TRY(hipMemcpyAsync(sc.ind.p, sr.ind.p, 4 * (size_t)M, hipMemcpyDeviceToDevice, s));
-      GRB_HIP_TRY(hipMemcpyAsync(sc.val.p, sr.val.p, 4 * (size_t)M, hipMemcpyDeviceToDevice, s));
-    }
+    if (both) GRB_TRY(side_mirror(&sc, sr, n, M, s));    // the structure is symmetric and so are the values: the CSC is a copy
   } else if (C) {
     GRB_HIP_TRY(hipMemsetAsync(sr.ptr.p, 0, 4 * ((size_t)n + 1), s));
     if (both) GRB_HIP_TRY(hipMemsetAsync(sc.ptr.p, 0, 4 * ((size_t)n + 1), s));
@@ -681,12 +554,7 @@ grb_info matching_run(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uns
   // everything that can fail is behind us, but the CSC's plan (attach builds it before it touches C) and two copies.  A, which
   // may be C, has been read for the last time
   if (C) GRB_TRY(attach(C, &sr, both ? &sc : nullptr));
-  if (n > 0) {
-    GRB_HIP_TRY(hipMemcpyAsync(mate->d_val, a.mate, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-    GRB_HIP_TRY(hipStreamSynchronize(s));
-  }
-  mate->vec_type = GRB_DENSE;
-  mate->d_nnz = n;
+  GRB_TRY(dense_out_commit(mate, a.mate, n, s));
   if (res) *res = r;
   return GRB_SUCCESS;
 }

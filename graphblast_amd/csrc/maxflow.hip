@@ -33,7 +33,7 @@
 // side = the last backward BFS from the sink.
 // Working memory: 44 bytes per vertex, 16 bytes per slot of R (at most 2 nvals + 3 n slots) and with F 4 bytes per entry of
 // A, one allocation.  R is proportional to nvals: the reverse arcs and the residuals have to live somewhere.
-#include "persist_common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -77,14 +77,6 @@ struct MfArgs {
   MfState* st;
 };
 
-__device__ __forceinline__ Index mf_lower_bound(const Index* __restrict__ a, Index lo, Index hi, Index x) {
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // the capacity of a stored value: mode 1: 1 and nothing is read; mode 0: i32 >= 0, f32 an integer value in 0 .. 2^24
 __device__ __forceinline__ unsigned mf_capacity(const unsigned* __restrict__ val, Index at, int f32, int unit, bool* bad) {
   if (unit) return 1u;
@@ -115,9 +107,9 @@ __global__ __launch_bounds__(kBlock) void mf_merge_kernel(const Index* __restric
   for (long long v = (long long)blockIdx.x * kWavesPerBlock + wave_id(); v < n; v += (long long)gridDim.x * kWavesPerBlock) {
     const Index rb = rptr[v], re = rptr[v + 1];
     const Index cb = cptr[v], ce = cptr[v + 1];
-    const Index dr = mf_lower_bound(rind, rb, re, (Index)v);             // where the diagonal lies, if stored
+    const Index dr = index_lower_bound(rind, rb, re, (Index)v);             // where the diagonal lies, if stored
     const bool has_r = dr < re && rind[dr] == (Index)v;
-    const Index dc = mf_lower_bound(cind, cb, ce, (Index)v);
+    const Index dc = index_lower_bound(cind, cb, ce, (Index)v);
     const bool has_c = dc < ce && cind[dc] == (Index)v;
     const long long base = kFill ? (long long)sptr[v] : 0;
     const unsigned room = kFill ? sptr[v + 1] - sptr[v] : 0u;
@@ -129,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void mf_merge_kernel(const Index* __restric
       Index pc = cb;
       bool found = false;
       if (keep) {
-        pc = mf_lower_bound(cind, cb, ce, u);
+        pc = index_lower_bound(cind, cb, ce, u);
         found = pc < ce && cind[pc] == u;
       }
       const unsigned long long bm = __ballot(found);
@@ -154,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void mf_merge_kernel(const Index* __restric
       Index pr = rb;
       bool found = false;
       if (keep) {
-        pr = mf_lower_bound(rind, rb, re, w);
+        pr = index_lower_bound(rind, rb, re, w);
         found = pr < re && rind[pr] == w;
       }
       const unsigned long long bm = __ballot(found);
@@ -206,51 +198,13 @@ __global__ __launch_bounds__(kBlock) void mf_twin_kernel(const Index* __restrict
       if ((unsigned)w < (unsigned)n) {
         const Index wb = rptr[w], we = rptr[w + 1];
         if (wb >= 0 && (long long)we <= slots) {
-          const Index at = mf_lower_bound(oth, wb, we, (Index)v);
+          const Index at = index_lower_bound(oth, wb, we, (Index)v);
           if (at < we && oth[at] == (Index)v) t = at;
         }
       }
       twin[p] = t;
     }
   }
-}
-
-// ---- a wave's staged appends of vertices (as in matching.hip) -----------------------------------------------------------------
-// cnt is the same in every lane; every lane of the wave calls these together
-struct MfOut {
-  Index* sv;                        // the wave's stage (LDS)
-  unsigned cnt;                     // staged
-  Index* dst;                       // the list the wave appends to, its counter, its room
-  unsigned* counter;
-  unsigned cap;
-};
-__device__ __forceinline__ void mf_flush(MfOut& o, int lane) {
-  if (o.cnt == 0u) return;
-  const unsigned cnt = o.cnt;
-  __builtin_amdgcn_wave_barrier();
-  unsigned at = 0;
-  if (lane == 0) at = atomicAdd(o.counter, cnt);
-  at = (unsigned)__shfl((int)at, 0, kWave);
-  for (unsigned i = (unsigned)lane; i < cnt; i += kWave)
-    if (at + i < o.cap) publish(&o.dst[at + i], o.sv[i]);                    // (always: a vertex enters a list once a pass)
-  __builtin_amdgcn_wave_barrier();
-  o.cnt = 0u;
-}
-__device__ __forceinline__ void mf_append(MfOut& o, int lane, bool want, Index v) {
-  const unsigned long long m = __ballot(want);
-  if (m == 0ull) return;
-  if (o.cnt + kWave > (unsigned)kMfStage) mf_flush(o, lane);
-  if (want) o.sv[o.cnt + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = v;
-  o.cnt += (unsigned)__popcll(m);
-}
-
-__device__ __forceinline__ unsigned long long mf_incl_scan_u64(unsigned long long v, int lane) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const unsigned long long t = __shfl_up(v, (unsigned)o, kWave);
-    if (lane >= o) v += t;
-  }
-  return v;
 }
 
 struct MfLds {
@@ -280,7 +234,7 @@ __device__ __forceinline__ bool mf_move(const MfArgs& a, const MfRound& r, Index
 // the push over the row [b, e) of u by kThreads threads (t: this one's number among them); whole waves call it together.
 // A step is a quad of slots a thread; the threads' admissible residuals before this one are an exclusive prefix sum.
 template <int kThreads>
-__device__ __forceinline__ void mf_push_walk(const MfArgs& a, const MfRound& r, MfOut& o, MfLds& L, Index u, Index hu, unsigned long long e0,
+__device__ __forceinline__ void mf_push_walk(const MfArgs& a, const MfRound& r, WaveStage& o, MfLds& L, Index u, Index hu, unsigned long long e0,
                                              Index b, Index e, int t, int lane, int wave) {
   const Index nq = (e - b) >> 2;
   unsigned long long rem = e0;
@@ -300,7 +254,7 @@ __device__ __forceinline__ void mf_push_walk(const MfArgs& a, const MfRound& r, 
       adm[j] = (unsigned)v[j] < (unsigned)a.n && hu == hv[j] + 1 ? fresh(&a.cap[at + j]) : 0u;
       s += adm[j];
     }
-    const unsigned long long incl = mf_incl_scan_u64(s, lane);
+    const unsigned long long incl = wave_incl_scan_u64(s);
     unsigned long long pre = incl - s, tot = __shfl(incl, kWave - 1, kWave);
     if (kThreads > kWave) {
       if (lane == 0) L.wtot[wave] = tot;
@@ -320,7 +274,7 @@ __device__ __forceinline__ void mf_push_walk(const MfArgs& a, const MfRound& r, 
       avail -= d;
       bool first = false;
       if (d > 0u) first = mf_move(a, r, at + j, v[j], adm[j], d);
-      mf_append(o, lane, first, v[j]);
+      stage_push<kMfStage>(o, lane, first, v[j]);
     }
     rem -= rem < tot ? rem : tot;
   }
@@ -328,7 +282,7 @@ __device__ __forceinline__ void mf_push_walk(const MfArgs& a, const MfRound& r, 
 }
 
 // the push pass over `count` queued vertices; the whole grid calls it together
-__device__ __forceinline__ void mf_push_rows(const MfArgs& a, const MfRound& r, MfOut& o, long long count, const Index* queue, MfLds& L, int tid,
+__device__ __forceinline__ void mf_push_rows(const MfArgs& a, const MfRound& r, WaveStage& o, long long count, const Index* queue, MfLds& L, int tid,
                                              int lane, int wave, long long gwave, long long gwaves) {
   for (long long base = 0; base < count; base += gwaves * kWave) {
     if (tid == 0) L.nbig = 0;
@@ -371,7 +325,7 @@ __device__ __forceinline__ void mf_push_rows(const MfArgs& a, const MfRound& r, 
               rem -= d;
             }
           }
-          mf_append(o, lane, first, v[j]);
+          stage_push<kMfStage>(o, lane, first, v[j]);
         }
       }
       if (mine) publish(&a.exc[u], (long long)rem);
@@ -406,7 +360,7 @@ struct MfLabel {
   static constexpr bool kBest = true;
   const MfArgs& a;
   const MfRound& r;
-  MfOut& o;
+  WaveStage& o;
   // x was evaluated in this round: its excess, its height in the next round's array; true: it is relabelled and queued
   __device__ __forceinline__ bool wanted(Index x) const {
     const unsigned long long got = fresh(&a.inc[x]);
@@ -450,7 +404,7 @@ struct MfLabel {
 struct MfBfs {
   static constexpr bool kBest = false;
   const MfArgs& a;
-  MfOut& o;
+  WaveStage& o;
   Index* d;
   Index label;
   __device__ __forceinline__ bool wanted(Index) const { return true; }
@@ -475,13 +429,14 @@ struct MfBfs {
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const bool won = ok[j] && du[j] == kMfUnset && atomicCAS(&d[u[j]], kMfUnset, label) == kMfUnset;
-      mf_append(o, lane, won, u[j]);                                         // (every lane of the wave is here)
+      stage_push<kMfStage>(o, lane, won, u[j]);                                         // (every lane of the wave is here)
     }
   }
   __device__ __forceinline__ void settle(Index, unsigned) {}
 };
 
-// the row [b, e) of v walked by kThreads threads, a quad of slots each a step; whole waves call it together
+// the row [b, e) of v walked by kThreads threads, a quad of slots each a step; whole waves call it together.  (R's rows begin
+// and end on a 16-byte boundary: there is no head or tail, so graph_common.hpp's quad_span has nothing to do here)
 template <int kThreads, typename Op>
 __device__ __forceinline__ void mf_walk(Op& op, const Index* oth, Index v, Index b, Index e, int t, int lane, unsigned& best) {
   const Index nq = (e - b) >> 2;
@@ -518,7 +473,7 @@ __device__ __forceinline__ void mf_rows(const MfArgs& a, Op& op, long long count
         else if (Op::kBest) op.settle(v, kMfNone);                           // (never: it has excess, so it has an arc)
       }
     }
-    if (kQueue) mf_append(op.o, lane, go, v);
+    if (kQueue) stage_push<kMfStage>(op.o, lane, go, v);
     const Index len = e - b;
     if (len > kMfWaveLen) L.big[atomicAdd(&L.nbig, 1)] = v;
     {                                                                        // the short rows, a lane each
@@ -643,11 +598,11 @@ __global__ __launch_bounds__(kPThreads) void maxflow_persistent_kernel(MfArgs a)
   auto bfs = [&](Index* d, long long fc, Index label) -> bool {
     long long levels = 0;
     while (fc > 0 && levels <= n) {
-      MfOut o = {s_stage[wave], 0u, qb, &st->slot[passes & 3u].a, (unsigned)a.n};
+      WaveStage o = {s_stage[wave], 0u, qb, &st->slot[passes & 3u].a, 0u, (unsigned)a.n};
       MfBfs op = {a, o, d, label};
       pass_begin();
       mf_rows<false>(a, op, fc, qa, s_rows, tid, lane, wave, gwave, gwaves);
-      mf_flush(o, lane);
+      stage_flush(o, lane);
       if (!pass_end()) return false;
       fc = clamp_n(fresh(&sl->a));
       Index* t = qa; qa = qb; qb = t;
@@ -678,7 +633,7 @@ __global__ __launch_bounds__(kPThreads) void maxflow_persistent_kernel(MfArgs a)
       // ---- global relabeling: exact heights in both arrays, the queue anew
       if (!label_all(hn, a.want_flow != 0)) return;
       ++qid;
-      MfOut o = {s_stage[wave], 0u, qa, &st->slot[passes & 3u].a, (unsigned)a.n};
+      WaveStage o = {s_stage[wave], 0u, qa, &st->slot[passes & 3u].a, 0u, (unsigned)a.n};
       pass_begin();
       for (long long base = 0; base < n; base += gthreads) {
         const long long v = base + gtid;
@@ -691,9 +646,9 @@ __global__ __launch_bounds__(kPThreads) void maxflow_persistent_kernel(MfArgs a)
           want = h < limit && v != a.source && v != a.sink && fresh(&a.exc[v]) > 0;
           if (want) publish(&a.stamp[v], qid);
         }
-        mf_append(o, lane, want, (Index)v);
+        stage_push<kMfStage>(o, lane, want, (Index)v);
       }
-      mf_flush(o, lane);
+      stage_flush(o, lane);
       if (!pass_end()) return;
       count = clamp_n(fresh(&sl->a));
       ++relabels;
@@ -708,16 +663,16 @@ __global__ __launch_bounds__(kPThreads) void maxflow_persistent_kernel(MfArgs a)
     const MfRound r = {hc, hn, limit, qid};
     // ---- push
     {
-      MfOut o = {s_stage[wave], 0u, a.rl, &st->slot[passes & 3u].b, (unsigned)a.n};
+      WaveStage o = {s_stage[wave], 0u, a.rl, &st->slot[passes & 3u].b, 0u, (unsigned)a.n};
       pass_begin();
       mf_push_rows(a, r, o, count, qa, s_rows, tid, lane, wave, gwave, gwaves);
-      mf_flush(o, lane);
+      stage_flush(o, lane);
       if (!pass_end()) return;
     }
     const long long received = clamp_n(fresh(&sl->b));
     // ---- relabel, and the next round's queue
     {
-      MfOut o = {s_stage[wave], 0u, qb, &st->slot[passes & 3u].a, (unsigned)a.n};
+      WaveStage o = {s_stage[wave], 0u, qb, &st->slot[passes & 3u].a, 0u, (unsigned)a.n};
       MfLabel op = {a, r, o};
       pass_begin();
       mf_rows<true>(a, op, count, qa, s_rows, tid, lane, wave, gwave, gwaves);
@@ -736,9 +691,9 @@ __global__ __launch_bounds__(kPThreads) void maxflow_persistent_kernel(MfArgs a)
             if (want) publish(&a.stamp[x], qid + 1u);
           }
         }
-        mf_append(o, lane, want, v);
+        stage_push<kMfStage>(o, lane, want, v);
       }
-      mf_flush(o, lane);
+      stage_flush(o, lane);
       if (!pass_end()) return;
     }
     since += (unsigned long long)count;
@@ -826,14 +781,6 @@ __global__ __launch_bounds__(kBlock) void mf_ptr_kernel(const Index* __restrict_
 
 namespace {
 
-struct MfEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~MfEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 grb_info maxflow_run(grb_matrix F, grb_vector side, grb_matrix A, Index source, Index sink, int mode, grb_maxflow_result* res) {
   GRB_TRY(ctx_init());
   Context& c = ctx();
@@ -845,25 +792,20 @@ grb_info maxflow_run(grb_matrix F, grb_vector side, grb_matrix A, Index source, 
   const bool both = F && F->format != 1;
   grb_maxflow_result r = {};
   Side sr, sc;
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, maxflow_persistent_kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
-  }
-  MfEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  GRB_TRY(persistent_kernel_fits(maxflow_persistent_kernel));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- one allocation: the state; per vertex the row pointers, excess, received, two heights, stamp, two queues, receivers;
   // per slot of R four words (2 nvals + 3 n slots at most, and never more than INT32_MAX); the flags of F's scan; the totals
   // of the two scans
   unsigned long long slots_ull = 2ull * (unsigned long long)nvals + 3ull * (unsigned long long)n;
   if (slots_ull > kMfMaxSlots) slots_ull = kMfMaxSlots;
-  const size_t slots = ((size_t)slots_ull + 63) & ~(size_t)63;
-  const size_t st_bytes = (sizeof(MfState) + 255) & ~(size_t)255;
-  const size_t vw = ((size_t)n + 1 + 63) & ~(size_t)63;
-  const size_t fw = F ? ((size_t)nvals + 1 + 63) & ~(size_t)63 : 0;
+  const size_t slots = pad_words((size_t)slots_ull);
+  const size_t st_bytes = pad_bytes(sizeof(MfState));
+  const size_t vw = pad_words((size_t)n + 1);
+  const size_t fw = F ? pad_words((size_t)nvals + 1) : 0;
   const size_t scan_n = (size_t)n + 1 > (size_t)nvals + 1 ? (size_t)n + 1 : (size_t)nvals + 1;
-  const size_t scan_bytes = (device_scan_u32_scratch((long long)scan_n) + 63) & ~(size_t)63;
+  const size_t scan_bytes = (device_scan_u32_scratch((long long)scan_n) + 63) & ~(size_t)63;   // (the last array: to 64 bytes)
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, st_bytes + 16 * vw + 4 * 7 * vw + 16 * slots + 4 * fw + scan_bytes + 64));
   MfArgs a;
@@ -892,13 +834,7 @@ grb_info maxflow_run(grb_matrix F, grb_vector side, grb_matrix A, Index source, 
   a.sink = sink;
   a.slots = (long long)slots_ull;
   a.want_flow = F ? 1 : 0;
-  // side's dense storage, before anything runs (allocates only where it has none yet); it stays as it was until the end
-  if (side) {
-    const int old_type = side->vec_type;
-    const grb_info si = grb_vector_set_storage(side, GRB_DENSE);
-    side->vec_type = old_type;
-    if (si != GRB_SUCCESS || !side->d_val) return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
-  }
+  if (side) GRB_TRY(dense_out_prepare(side, n));         // before anything runs; side stays as it was until the end
   GRB_TRY(bfs_lanes_fence(s));      // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
   GRB_HIP_TRY(hipEventRecord(ev.a, s));
   GRB_HIP_TRY(hipMemsetAsync(work.p, 0, st_bytes, s));
@@ -989,12 +925,7 @@ grb_info maxflow_run(grb_matrix F, grb_vector side, grb_matrix A, Index source, 
   // everything that can fail is behind us, but the CSC's plan (attach builds it before it touches F) and one copy.  A, which
   // may be F, has been read for the last time
   if (F) GRB_TRY(attach(F, &sr, both ? &sc : nullptr));
-  if (side) {
-    GRB_HIP_TRY(hipMemcpyAsync(side->d_val, a.stamp, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-    GRB_HIP_TRY(hipStreamSynchronize(s));
-    side->vec_type = GRB_DENSE;
-    side->d_nnz = n;
-  }
+  if (side) GRB_TRY(dense_out_commit(side, a.stamp, n, s));
   if (res) *res = r;
   return GRB_SUCCESS;
 }

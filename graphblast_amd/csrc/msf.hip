@@ -31,7 +31,7 @@
 // lower bound per row, and the weight is a two-level sum whose shape depends on the number of entries alone.
 // Working memory: 56 bytes per vertex and 4.3 KiB (the state and the partial sums), one allocation; the sort brings 24
 // more per vertex of its own.
-#include "persist_common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -55,7 +55,7 @@ struct MsState {                    // zeroed by the host before the launch
   GridBarrier bar;
   MsSlot slot[4];                   // pass p adds into slot[p & 3]; workgroup 0 clears slot[(p + 2) & 3] meanwhile
   unsigned forest[32];              // forest edges appended so far (only pass C adds, and everybody reads it before the next one)
-  unsigned flag[32];                // ms_compare_kernel: 1 = the CSR and the CSC differ
+  unsigned flag[32];                // the symmetry check (graph_common.hpp): 1 = the CSR and the CSC differ
   unsigned long long rec[kMsRec];   // [0] off-diagonal entries [1] forest edges [2] components [3] isolated [4] rounds [5] passes
                                     // [6] done [7] a NaN off the diagonal
 };
@@ -72,27 +72,6 @@ struct MsArgs {
   Index *cand, *fv, *fpos;
   MsState* st;
 };
-
-// the monotone map of a weight's bits to an unsigned: f32 by value with -0 = +0, i32 as a signed integer
-__device__ __forceinline__ unsigned ms_canon(unsigned b, int f32) { return f32 && b == 0x80000000u ? 0u : b; }
-__device__ __forceinline__ unsigned ms_order(unsigned b, int f32) {
-  if (!f32) return b ^ 0x80000000u;
-  b = ms_canon(b, 1);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// flag |= 1 when the CSR and the CSC differ: pointers, indices, values as bits with -0 taken as +0
-__global__ __launch_bounds__(kBlock) void ms_compare_kernel(const Index* __restrict__ a_ptr, const Index* __restrict__ b_ptr, long long n1,
-                                                            const Index* __restrict__ a_ind, const Index* __restrict__ b_ind,
-                                                            const unsigned* __restrict__ a_val, const unsigned* __restrict__ b_val, long long nnz,
-                                                            int f32, unsigned int* __restrict__ flag) {
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n1 + nnz; i += (long long)gridDim.x * kBlock) {
-    if (i < n1) bad |= a_ptr[i] != b_ptr[i];
-    else bad |= a_ind[i - n1] != b_ind[i - n1] || ms_canon(a_val[i - n1], f32) != ms_canon(b_val[i - n1], f32);
-  }
-  if (__ballot(bad) != 0ull && lane_id() == 0) atomicOr(flag, 1u);
-}
 
 // ---- a wave's staged appends of (vertex, position) -------------------------------------------------------------------------
 // cnt is the same in every lane; every lane of the wave calls these together
@@ -148,7 +127,7 @@ __device__ __forceinline__ void ms_hit(const MsArgs& a, Index v, int c, const In
   for (int j = 0; j < N; ++j)
     if (ok[j]) {
       if (a.f32 && (w[j] & 0x7fffffffu) > 0x7f800000u) nan = true;
-      const unsigned long long key = ((unsigned long long)ms_order(w[j], a.f32) << 32) | (unsigned)u[j];
+      const unsigned long long key = ((unsigned long long)weight_order(w[j], a.f32) << 32) | (unsigned)u[j];
       if (key < best) { best = key; bpos = p[j]; }
     }
 }
@@ -156,12 +135,9 @@ __device__ __forceinline__ void ms_hit(const MsArgs& a, Index v, int c, const In
 // the row [b, e) of v walked by kThreads threads (t: this one's number among them)
 template <int kThreads>
 __device__ __forceinline__ void ms_walk(const MsArgs& a, Index v, int c, Index b, Index e, int t, unsigned long long& best, Index& bpos, bool& nan) {
-  // up to three entries before the first 16-byte boundary, whole quads, up to three entries behind them
-  Index b4 = b + (Index)((4u - (unsigned)((reinterpret_cast<uintptr_t>(a.ind + b) >> 2) & 3u)) & 3u);
-  if (b4 > e) b4 = e;
-  const Index nq = (e - b4) >> 2, te = b4 + 4 * nq;
+  const QuadSpan s = quad_span(a.ind, b, e);
+  const Index b4 = s.b4, nq = s.nq, te = s.te, nh = s.nh, ns = s.ns;
   if (kThreads == kWave || t < kWave) {
-    const Index nh = b4 - b, ns = nh + (e - te);
     Index u[1] = {0}, p[1] = {0};
     bool ok[1] = {t < ns};
     if (ok[0]) {
@@ -201,20 +177,8 @@ __device__ __forceinline__ bool ms_edge(const MsArgs& a, Index v, Index pos, Ind
   if ((unsigned)u >= (unsigned)a.n) return false;
   const unsigned lo = (unsigned)(u < v ? u : v);
   mx = (unsigned)(u < v ? v : u);
-  k64 = ((unsigned long long)ms_order(a.val[pos], a.f32) << 32) | lo;
+  k64 = ((unsigned long long)weight_order(a.val[pos], a.f32) << 32) | lo;
   return true;
-}
-
-// the length of v's row without a stored diagonal (indices ascending)
-__device__ __forceinline__ int ms_degree(const MsArgs& a, Index v) {
-  const Index b = a.ptr[v], e = a.ptr[v + 1];
-  Index lo = b, hi = e;
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a.ind[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  const int d = (int)(e - b) - (lo < e && a.ind[lo] == v ? 1 : 0);
-  return d > 0 ? d : 0;
 }
 
 __global__ __launch_bounds__(kPThreads) void msf_persistent_kernel(MsArgs a) {
@@ -277,7 +241,7 @@ __global__ __launch_bounds__(kPThreads) void msf_persistent_kernel(MsArgs a) {
     unsigned long long my_sum = 0;
     pass_begin();
     for (long long v = gtid; v < n; v += gthreads) {
-      const int d = ms_degree(a, (Index)v);
+      const int d = row_degree_no_diag(a.ptr, a.ind, (Index)v);
       publish(&a.comp[v], (int)v);
       publish(&a.parent[v], (int)v);
       publish(&a.best[v], kMsNone);
@@ -497,12 +461,7 @@ __global__ __launch_bounds__(kBlock) void ms_expand_kernel(const Index* __restri
     if ((unsigned)u >= (unsigned)n) u = v;                                   // (never)
     unsigned w = val[pos];
     if (u < v) {                                                             // v's twin entry in row u
-      Index lo = ptr[u], hi = ptr[u + 1];
-      const Index e = hi;
-      while (lo < hi) {
-        const Index mid = lo + ((hi - lo) >> 1);
-        if (ind[mid] < v) lo = mid + 1; else hi = mid;
-      }
+      const Index e = ptr[u + 1], lo = index_lower_bound(ind, ptr[u], e, v);
       if (lo < e && ind[lo] == v) w = val[lo];
     }
     keys[2 * i] = ((unsigned long long)(unsigned)v << 32) | (unsigned)u;
@@ -532,12 +491,10 @@ __global__ __launch_bounds__(kBlock) void ms_rows_kernel(const unsigned long lon
 }
 
 // the weight over the entries above the diagonal, each edge once: block b adds the entries b * kBlock + t + k * blocks * kBlock in
-// the order of k, its threads' sums by a fixed butterfly, and the last kernel adds the blocks' sums in order.  kF32: f64 sums;
-// else exact 64-bit integer sums.
+// the order of k; the rest of the sum is graph_common.hpp's fixed-order tail (weight_block_sum, weight_final_kernel)
 template <bool kF32>
 __global__ __launch_bounds__(kBlock) void ms_weight_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ pay, long long m,
                                                            unsigned long long* __restrict__ partial) {
-  __shared__ unsigned long long s_part[kWavesPerBlock];
   double fs = 0.0;
   long long is = 0;
   for (long long j = (long long)blockIdx.x * kBlock + threadIdx.x; j < m; j += (long long)gridDim.x * kBlock) {
@@ -547,57 +504,10 @@ __global__ __launch_bounds__(kBlock) void ms_weight_kernel(const unsigned long l
       else is += (long long)(int)pay[j];
     }
   }
-  for (int s = kWave / 2; s > 0; s >>= 1) {
-    if (kF32) fs += __shfl_xor(fs, s, kWave);
-    else is += __shfl_xor(is, s, kWave);
-  }
-  if (lane_id() == 0) s_part[wave_id()] = kF32 ? (unsigned long long)__double_as_longlong(fs) : (unsigned long long)is;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWavesPerBlock; ++w) {
-      if (kF32) fs += __longlong_as_double((long long)s_part[w]);
-      else is += (long long)s_part[w];
-    }
-    partial[blockIdx.x] = kF32 ? (unsigned long long)__double_as_longlong(fs) : (unsigned long long)is;
-  }
-}
-template <bool kF32>
-__global__ void ms_weight_final_kernel(const unsigned long long* __restrict__ partial, int blocks, double* __restrict__ out) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double fs = 0.0;
-  long long is = 0;
-  for (int b = 0; b < blocks; ++b) {
-    if (kF32) fs += __longlong_as_double((long long)partial[b]);
-    else is += (long long)partial[b];
-  }
-  *out = kF32 ? fs : (double)is;
+  weight_block_sum<kF32>(fs, is, partial);
 }
 
 namespace {
-
-struct MsEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~MsEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
-inline int ms_bits(Index dim) {
-  int b = 1;
-  while (b < 31 && ((long long)1 << b) < (long long)dim) ++b;
-  return b;
-}
-
-// C's arrays for m entries, exactly
-grb_info ms_side(Side* sd, Index n, long long m) {
-  GRB_TRY(ewm_alloc(&sd->ptr, 4 * ((size_t)n + 1)));
-  GRB_TRY(ewm_alloc(&sd->ind, 4 * (size_t)(m > 0 ? m : 1)));
-  GRB_TRY(ewm_alloc(&sd->val, 4 * (size_t)(m > 0 ? m : 1)));
-  sd->nnz = (Index)m;
-  sd->h_ptr.assign((size_t)n + 1, 0);
-  return GRB_SUCCESS;
-}
 
 grb_info msf_run(grb_matrix C, grb_vector comp, grb_matrix A, grb_msf_result* res) {
   GRB_TRY(ctx_init());
@@ -605,23 +515,15 @@ grb_info msf_run(grb_matrix C, grb_vector comp, grb_matrix A, grb_msf_result* re
   hipStream_t s = c.stream;
   const Index n = A->nrows;
   const int f32 = A->dtype == GRB_F32 ? 1 : 0;
-  const bool own_csc = !A->csc_alias && A->csc.ptr != nullptr;
   const bool both = C->format != 1;
   grb_msf_result r = {};
   Side sr, sc;
-  if (n > 0) {
-    static int max_per_cu = 0;
-    if (!max_per_cu) {
-      GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, msf_persistent_kernel, kPThreads, 0));
-      if (max_per_cu < 1) return GRB_PANIC;
-    }
-  }
-  MsEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  if (n > 0) GRB_TRY(persistent_kernel_fits(msf_persistent_kernel));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- one allocation: the state, best (8 bytes), six words per vertex, then the pairs of both directions and the partial sums
-  const size_t st_bytes = (sizeof(MsState) + 255) & ~(size_t)255;
-  const size_t vw = ((size_t)n + 63) & ~(size_t)63;
+  const size_t st_bytes = pad_bytes(sizeof(MsState));
+  const size_t vw = pad_words((size_t)n);
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, st_bytes + 56 * vw + 8 * (size_t)kMsSumBlocks + 64));
   MsArgs a;
@@ -642,22 +544,13 @@ grb_info msf_run(grb_matrix C, grb_vector comp, grb_matrix A, grb_msf_result* re
   unsigned* d_pay = (unsigned*)(d_keys + 2 * vw);                            // [2 vw]
   unsigned long long* d_partial = (unsigned long long*)(d_pay + 2 * vw);     // [kMsSumBlocks]
   double* d_weight = (double*)(d_partial + kMsSumBlocks);
-  // comp's dense storage, before anything runs (allocates only where it has none yet); it stays as it was until the end
-  if (comp) {
-    const int old_type = comp->vec_type;
-    const grb_info si = grb_vector_set_storage(comp, GRB_DENSE);
-    comp->vec_type = old_type;
-    if (si != GRB_SUCCESS || (n > 0 && !comp->d_val)) return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
-  }
+  if (comp) GRB_TRY(dense_out_prepare(comp, n));         // before anything runs; comp stays as it was until the end
   long long F = 0;
   if (n > 0) {
     GRB_TRY(bfs_lanes_fence(s));    // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
     GRB_HIP_TRY(hipEventRecord(ev.a, s));
     GRB_HIP_TRY(hipMemsetAsync(work.p, 0, st_bytes, s));
-    if (own_csc)
-      hipLaunchKernelGGL(ms_compare_kernel, dim3(stream_grid((long long)n + 1 + (long long)A->nvals)), dim3(kBlock), 0, s, A->csr.ptr, A->csc.ptr,
-                         (long long)n + 1, A->csr.ind, A->csc.ind, (const unsigned*)A->csr.val, (const unsigned*)A->csc.val,
-                         (long long)A->nvals, f32, &a.st->flag[0]);
+    launch_symmetry_check<true>(A, &a.st->flag[0], s);
     hipLaunchKernelGGL(msf_persistent_kernel, dim3(c.num_cu), dim3(kPThreads), 0, s, a);
     GRB_HIP_TRY(hipGetLastError());
     struct { unsigned flag[32]; unsigned long long rec[kMsRec]; } h;
@@ -678,31 +571,27 @@ grb_info msf_run(grb_matrix C, grb_vector comp, grb_matrix A, grb_msf_result* re
   }
   // ---- C's arrays
   const long long m = 2 * F;
-  GRB_TRY(ms_side(&sr, n, m));
-  if (both) GRB_TRY(ms_side(&sc, n, m));
+  GRB_TRY(side_alloc(&sr, n, m));
+  if (both) GRB_TRY(side_alloc(&sc, n, m));
   if (m > 0) {
     hipLaunchKernelGGL(ms_expand_kernel, dim3(stream_grid(F)), dim3(kBlock), 0, s, A->csr.ptr, A->csr.ind, (const unsigned*)A->csr.val, n,
                        a.fv, a.fpos, F, d_keys, d_pay);
     GRB_HIP_TRY(hipGetLastError());
-    GRB_TRY(device_sort_pairs(d_keys, d_pay, m, ms_bits(n), ms_bits(n)));
+    GRB_TRY(device_sort_pairs(d_keys, d_pay, m, key_bits(n), key_bits(n)));
     hipLaunchKernelGGL(ms_rows_kernel, dim3(stream_grid((long long)n + 1 + m)), dim3(kBlock), 0, s, d_keys, d_pay, m, (long long)n + 1,
                        (Index*)sr.ptr.p, (Index*)sr.ind.p, (unsigned*)sr.val.p);
     const int blocks = (int)((m + kBlock - 1) / kBlock < kMsSumBlocks ? (m + kBlock - 1) / kBlock : kMsSumBlocks);
     if (f32) {
       hipLaunchKernelGGL(ms_weight_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, d_keys, d_pay, m, d_partial);
-      hipLaunchKernelGGL(ms_weight_final_kernel<true>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
+      hipLaunchKernelGGL(weight_final_kernel<true>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
     } else {
       hipLaunchKernelGGL(ms_weight_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, d_keys, d_pay, m, d_partial);
-      hipLaunchKernelGGL(ms_weight_final_kernel<false>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
+      hipLaunchKernelGGL(weight_final_kernel<false>, dim3(1), dim3(kWave), 0, s, d_partial, blocks, d_weight);
     }
     GRB_HIP_TRY(hipGetLastError());
     GRB_HIP_TRY(hipMemcpyAsync(&r.weight, d_weight, 8, hipMemcpyDeviceToHost, s));
     GRB_HIP_TRY(hipMemcpyAsync(sr.h_ptr.data(), sr.ptr.p, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost, s));
-    if (both) {                                          // the structure is symmetric and so are the values: the CSC is a copy
-      GRB_HIP_TRY(hipMemcpyAsync(sc.ptr.p, sr.ptr.p, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
-      GRB_HIP_TRY(hipMemcpyAsync(sc.ind.p, sr.ind.p, 4 * (size_t)m, hipMemcpyDeviceToDevice, s));
-      GRB_HIP_TRY(hipMemcpyAsync(sc.val.p, sr.val.p, 4 * (size_t)m, hipMemcpyDeviceToDevice, s));
-    }
+    if (both) GRB_TRY(side_mirror(&sc, sr, n, m, s));    // the structure is symmetric and so are the values: the CSC is a copy
   } else {
     GRB_HIP_TRY(hipMemsetAsync(sr.ptr.p, 0, 4 * ((size_t)n + 1), s));
     if (both) GRB_HIP_TRY(hipMemsetAsync(sc.ptr.p, 0, 4 * ((size_t)n + 1), s));
@@ -718,14 +607,7 @@ grb_info msf_run(grb_matrix C, grb_vector comp, grb_matrix A, grb_msf_result* re
   // everything that can fail is behind us, but the CSC's plan (attach builds it before it touches C) and two copies.  A, which
   // may be C, has been read for the last time
   GRB_TRY(attach(C, &sr, both ? &sc : nullptr));
-  if (comp) {
-    if (n > 0) {
-      GRB_HIP_TRY(hipMemcpyAsync(comp->d_val, a.comp, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-      GRB_HIP_TRY(hipStreamSynchronize(s));
-    }
-    comp->vec_type = GRB_DENSE;
-    comp->d_nnz = n;
-  }
+  if (comp) GRB_TRY(dense_out_commit(comp, a.comp, n, s));
   if (res) *res = r;
   return GRB_SUCCESS;
 }

@@ -37,7 +37,7 @@
 //            counter (four slots in rotation, see kcore.hip for why a shared tail will not do).
 // Working memory: state, din, dout, colour, order, qb: 24 bytes per vertex, and 2 KiB of state, one allocation.
 #include <type_traits>
-#include "persist_common.hpp"
+#include "graph_common.hpp"
 
 namespace grb {
 
@@ -74,43 +74,6 @@ struct ScArgs {
 
 enum { kScDecIn = 0, kScDecOut, kScFwd, kScBwd, kScProp, kScCollect };
 
-__device__ __forceinline__ unsigned long long sc_wave_max_u64(unsigned long long v) {
-  for (int s = kWave / 2; s > 0; s >>= 1) {
-    const unsigned long long o = __shfl_xor(v, s, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-// ---- a wave's staged appends ----------------------------------------------------------------------------------------------
-// cnt is the same in every lane; every lane of the wave calls these together
-struct ScOut {
-  Index* stage;                     // the wave's stage (LDS)
-  unsigned cnt;                     // staged
-  unsigned* added;                  // the pass's counter
-  Index* buf;                       // where the pass appends: buf[base + ...], below cap
-  unsigned base, cap;
-};
-__device__ __forceinline__ void sc_flush(ScOut& o, int lane) {
-  if (o.cnt == 0u) return;
-  const unsigned cnt = o.cnt;
-  __builtin_amdgcn_wave_barrier();
-  unsigned at = 0;
-  if (lane == 0) at = atomicAdd(o.added, cnt);
-  at = o.base + (unsigned)__shfl((int)at, 0, kWave);
-  for (unsigned i = (unsigned)lane; i < cnt; i += kWave)
-    if (at + i < o.cap) publish(&o.buf[at + i], o.stage[i]);                 // (always: a pass appends a vertex once)
-  __builtin_amdgcn_wave_barrier();
-  o.cnt = 0u;
-}
-__device__ __forceinline__ void sc_push(ScOut& o, int lane, bool want, Index u) {
-  const unsigned long long m = __ballot(want);
-  if (m == 0ull) return;
-  if (o.cnt + kWave > (unsigned)kScStage) sc_flush(o, lane);
-  if (want) o.stage[o.cnt + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = u;
-  o.cnt += (unsigned)__popcll(m);
-}
-
 // ---- what a pass does to the neighbour u (state word s) of its vertex v (colour c); true: this thread appends u -----------
 template <int OP>
 __device__ __forceinline__ bool sc_apply(const ScArgs& a, Index v, int c, unsigned qbit, Index u, unsigned s) {
@@ -144,7 +107,7 @@ __device__ __forceinline__ bool sc_apply(const ScArgs& a, Index v, int c, unsign
 
 // up to N neighbours: the state loads, then the work, then the appends
 template <int OP, int N>
-__device__ __forceinline__ void sc_hit(const ScArgs& a, Index v, int c, unsigned qbit, const Index (&u)[N], bool (&ok)[N], ScOut& o, int lane,
+__device__ __forceinline__ void sc_hit(const ScArgs& a, Index v, int c, unsigned qbit, const Index (&u)[N], bool (&ok)[N], WaveStage& o, int lane,
                                        unsigned& low) {
   unsigned s[N];
 #pragma unroll
@@ -157,20 +120,17 @@ __device__ __forceinline__ void sc_hit(const ScArgs& a, Index v, int c, unsigned
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     if (OP == kScBwd && ok[j] && (unsigned)u[j] < low) low = (unsigned)u[j];
-    sc_push(o, lane, ok[j], u[j]);
+    stage_push<kScStage>(o, lane, ok[j], u[j]);
   }
 }
 
 // the list [b, e) of v walked by kThreads threads (t: this one's number among them); every lane of every wave of them calls it
 template <int OP, int kThreads>
 __device__ __forceinline__ void sc_walk(const ScArgs& a, const Index* __restrict__ ind, Index b, Index e, int t, int lane, Index v, int c,
-                                        unsigned qbit, ScOut& o, unsigned& low) {
-  // up to three entries before the first 16-byte boundary, whole quads, up to three entries behind them
-  Index b4 = b + (Index)((4u - (unsigned)((reinterpret_cast<uintptr_t>(ind + b) >> 2) & 3u)) & 3u);
-  if (b4 > e) b4 = e;
-  const Index nq = (e - b4) >> 2, te = b4 + 4 * nq;
+                                        unsigned qbit, WaveStage& o, unsigned& low) {
+  const QuadSpan s = quad_span(ind, b, e);
+  const Index b4 = s.b4, nq = s.nq, te = s.te, nh = s.nh, ns = s.ns;
   if (kThreads == kWave || t < kWave) {
-    const Index nh = b4 - b, ns = nh + (e - te);
     Index u[1] = {0};
     bool ok[1] = {t < ns};
     if (ok[0]) u[0] = ind[t < nh ? b + t : te + (t - nh)];
@@ -189,7 +149,7 @@ __device__ __forceinline__ void sc_walk(const ScArgs& a, const Index* __restrict
 // one direction of one pass: the lists (ptr, ind) of the F vertices q[0 .. F) are walked.  Every thread of the grid calls it.
 template <int OP>
 __device__ __forceinline__ void sc_sweep(const ScArgs& a, const Index* __restrict__ ptr, const Index* __restrict__ ind, const Index* q,
-                                         unsigned F, unsigned qclear, unsigned qbit, ScOut& o, Index* s_big, int* s_nbig, unsigned& low) {
+                                         unsigned F, unsigned qclear, unsigned qbit, WaveStage& o, Index* s_big, int* s_nbig, unsigned& low) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
   const long long gwave = (long long)wave * gridDim.x + blockIdx.x, gwaves = (long long)gridDim.x * kPWaves;   // neighbouring chunks: different CUs
   const unsigned per = F >= (unsigned long long)gwaves * kWave ? (unsigned)kWave : (unsigned)((F + gwaves - 1) / gwaves);
@@ -243,18 +203,6 @@ __device__ __forceinline__ void sc_sweep(const ScArgs& a, const Index* __restric
   }
 }
 
-// the length of v's list without a stored diagonal (indices ascending)
-__device__ __forceinline__ int sc_degree(const Index* __restrict__ ptr, const Index* __restrict__ ind, Index v) {
-  const Index b = ptr[v], e = ptr[v + 1];
-  Index lo = b, hi = e;
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (ind[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  const int d = (int)(e - b) - (lo < e && ind[lo] == v ? 1 : 0);
-  return d > 0 ? d : 0;
-}
-
 __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
   __shared__ Index s_stage[kPWaves][kScStage];
   __shared__ Index s_big[kPThreads];
@@ -264,7 +212,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
   const long long gtid = (long long)blockIdx.x * kPThreads + tid;
   const long long gthreads = (long long)gridDim.x * kPThreads;
   ScState* st = a.st;
-  ScOut o = {s_stage[wave], 0u, &st->slot[0].added, a.order, 0u, 0u};
+  WaveStage o = {s_stage[wave], 0u, a.order, &st->slot[0].added, 0u, 0u};
   unsigned gen = 0;
   const long long n = a.n;
   const unsigned un = (unsigned)a.n;
@@ -279,8 +227,8 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
   // a pass begins: its slot, the one after the next cleared, where it appends; and ends: the barrier, then what it appended
   auto pass_begin = [&](Index* buf, unsigned base) {
     sl = &st->slot[passes & 3u];
-    o.added = &sl->added;
-    o.buf = buf;
+    o.counter = &sl->added;
+    o.dst = buf;
     o.base = base;
     o.cap = un;
     if (blockIdx.x == 0 && tid == 0) {
@@ -292,7 +240,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
     }
   };
   auto pass_end = [&](unsigned& added) -> bool {
-    sc_flush(o, lane);
+    stage_flush(o, lane);
     if (!grid_sync(&st->bar, gen, false)) return false;
     added = fresh(&sl->added);
     ++passes;
@@ -300,7 +248,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
   };
   // the workgroup's part of a pass's sums, one atomic each
   auto reduce = [&](unsigned long long mx, unsigned inv, unsigned long long sum) {
-    mx = sc_wave_max_u64(mx);
+    mx = wave_max_u64(mx);
     inv = wave_max_u32(inv);
     sum = wave_sum_u64(sum);
     if (lane == 0) { s_red[wave][0] = mx; s_red[wave][1] = inv; s_red[wave][2] = sum; }
@@ -358,7 +306,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
       const bool ok = v < n;
       bool dead = false;
       if (ok) {
-        const int di = sc_degree(a.cptr, a.cind, (Index)v), dq = sc_degree(a.rptr, a.rind, (Index)v);
+        const int di = row_degree_no_diag(a.cptr, a.cind, (Index)v), dq = row_degree_no_diag(a.rptr, a.rind, (Index)v);
         dead = di == 0 || dq == 0;
         publish(&a.din[v], di);
         publish(&a.dout[v], dq);
@@ -366,7 +314,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
         publish(&a.state[v], dead ? 0u : kScLive);
         my_sum += (unsigned long long)dq;
       }
-      sc_push(o, lane, dead, (Index)v);
+      stage_push<kScStage>(o, lane, dead, (Index)v);
     }
     reduce(0ull, 0u, my_sum);
     if (!pass_end(added)) return;
@@ -412,7 +360,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
             publish(&a.state[pivot], kScF);
             atomicMax(&st->giant_inv_min[0], ~pivot);
           }
-          sc_push(o, lane, lane == 0, (Index)pivot);
+          stage_push<kScStage>(o, lane, lane == 0, (Index)pivot);
         }
         if (!pass_end(added)) return;
         tail = tail + added > un ? un : tail + added;
@@ -461,7 +409,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
       const long long v = base + gtid;
       const bool live = v < n && (fresh(&a.state[v]) & kScLive);
       if (live) publish(&a.colour[v], (int)v);
-      sc_push(o, lane, live, (Index)v);
+      stage_push<kScStage>(o, lane, live, (Index)v);
     }
     if (!pass_end(added)) return;
     {
@@ -495,7 +443,7 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
           publish(&a.din[v], 1);
         }
       }
-      sc_push(o, lane, root, (Index)v);
+      stage_push<kScStage>(o, lane, root, (Index)v);
     }
     if (!pass_end(added)) return;
     const unsigned nroots = added > un - tail ? un - tail : added;
@@ -538,14 +486,6 @@ __global__ __launch_bounds__(kPThreads) void scc_persistent_kernel(ScArgs a) {
 
 namespace {
 
-struct ScEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~ScEvents() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 grb_info scc_empty(grb_vector out, grb_scc_result* res) {                    // n = 0
   GRB_TRY(ctx_init());
   GRB_TRY(grb_vector_set_storage(out, GRB_DENSE));
@@ -561,17 +501,12 @@ grb_info scc_run(grb_vector out, grb_matrix A, grb_scc_result* res) {
   Context& c = ctx();
   hipStream_t s = c.stream;
   const Index n = A->nrows;
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, scc_persistent_kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
-  }
-  ScEvents ev;
-  GRB_HIP_TRY(hipEventCreate(&ev.a));
-  GRB_HIP_TRY(hipEventCreate(&ev.b));
+  GRB_TRY(persistent_kernel_fits(scc_persistent_kernel));
+  EventPair ev;
+  GRB_TRY(ev.create());
   // ---- one allocation: the state, then six arrays of a word per vertex
-  const size_t st_bytes = (sizeof(ScState) + 255) & ~(size_t)255;
-  const size_t vw = ((size_t)n + 63) & ~(size_t)63;
+  const size_t st_bytes = pad_bytes(sizeof(ScState));
+  const size_t vw = pad_words((size_t)n);
   EwmBuf work;
   GRB_TRY(ewm_alloc(&work, st_bytes + 24 * vw));
   ScArgs a;
@@ -587,11 +522,7 @@ grb_info scc_run(grb_vector out, grb_matrix A, grb_scc_result* res) {
   a.colour = a.dout + vw;
   a.order = (Index*)(a.colour + vw);
   a.qb = a.order + vw;
-  // the output's dense storage, before anything runs (allocates only where it has none yet); it stays as it was until the end
-  const int old_type = out->vec_type;
-  const grb_info si = grb_vector_set_storage(out, GRB_DENSE);
-  out->vec_type = old_type;
-  if (si != GRB_SUCCESS || !out->d_val) return si != GRB_SUCCESS ? si : GRB_OUT_OF_MEMORY;
+  GRB_TRY(dense_out_prepare(out, n));                    // before anything runs; out stays as it was until the end
 
   GRB_TRY(bfs_lanes_fence(s));      // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
   GRB_HIP_TRY(hipEventRecord(ev.a, s));
@@ -603,10 +534,7 @@ grb_info scc_run(grb_vector out, grb_matrix A, grb_scc_result* res) {
   GRB_HIP_TRY(hipMemcpyAsync(h_rec, a.st->rec, sizeof(h_rec), hipMemcpyDeviceToHost, s));
   GRB_HIP_TRY(hipStreamSynchronize(s));                  // the call's one read
   if (h_rec[kScDone] != 1ull) return GRB_PANIC;          // a grid barrier gave up
-  GRB_HIP_TRY(hipMemcpyAsync(out->d_val, a.colour, 4 * (size_t)n, hipMemcpyDeviceToDevice, s));
-  GRB_HIP_TRY(hipStreamSynchronize(s));
-  out->vec_type = GRB_DENSE;
-  out->d_nnz = n;
+  GRB_TRY(dense_out_commit(out, a.colour, n, s));
   grb_scc_result r = {};
   r.edges = (int64_t)h_rec[0];
   r.components = (int32_t)h_rec[1];
