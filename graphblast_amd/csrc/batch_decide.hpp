@@ -11,6 +11,13 @@
 // (sum over all sources under the point) - (sum over those of them before s in the order) is over the budget.  That form
 // needs no sorted array: a lane per source counts its predecessors.  Every sum is a sum of integers below 2^53 (at most
 // 64 * nvals), exact in doubles in any order and equal to the integer sum: both forms compare the same doubles.
+//
+// The finishing rule, after the per-source decisions.  A source near its END is under the switch point too, because almost
+// nothing is left for it to find -- and pushing it costs a pass over all n frontier words and a pass to count what arrived,
+// for a few thousand edges.  The rows that still lack its bit are rows the level's pull walks anyway.  U = the in-edges of
+// the rows that the pull of the level before left open (lacking a bit of some source it pulled), known and complete only
+// when that level pulled EVERY live source.  When the rule is push-pull, the per-source decisions pull some sources and
+// push others, U is known and U <= finish_limit * nvals, the pushed sources are pulled as well: q |= p, p = 0.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -35,7 +42,11 @@ struct BatchRule {
   float switchpoint;
   double budget;        // share of nvals that may be pushed in one level
   double tail_limit;    // out-edges a level may push inside the light-level launch; 0: no such launch
+  double finish_limit = -1.0;   // the finishing rule: the share of nvals up to which the open rows' in-edges make a level
+                                // pull its pushed sources too; below 0: no such rule
 };
+
+constexpr long long kOpenUnknown = -1;   // U of the level before: not counted, or that level did not pull every live source
 
 struct BatchDecision {
   unsigned long long qmask, pmask;   // bits pulled / pushed
@@ -85,8 +96,14 @@ GRB_DECIDE_HD inline unsigned long long batch_decide_stash(unsigned long long pm
   return kind == kDecideHost && pmask != 0 && batch_decide_heavy(pushed_edges, n) ? pmask : 0ull;
 }
 
+// the finishing rule: the level that would pull q and push p pulls both
+GRB_DECIDE_HD inline bool batch_decide_finish(unsigned long long qmask, unsigned long long pmask, const BatchRule& r, long long open_u) {
+  return r.mode == kDecidePushPull && qmask != 0 && pmask != 0 && open_u >= 0 && r.finish_limit >= 0 &&
+         (double)open_u <= r.finish_limit * (double)r.nvals;
+}
+
 GRB_DECIDE_HD inline BatchDecision batch_decide(const unsigned long long* nf_s, const unsigned long long* mf_s,
-                                                const BatchRule& r, bool iteration_left) {
+                                                const BatchRule& r, bool iteration_left, long long open_u = kOpenUnknown) {
   BatchDecision d;
   d.qmask = 0; d.pmask = 0; d.pushed_edges = 0;
   unsigned long long under = 0;
@@ -97,6 +114,7 @@ GRB_DECIDE_HD inline BatchDecision batch_decide(const unsigned long long* nf_s, 
     if (w == 2) d.qmask |= 1ull << s;
     if (w == 1) { d.pmask |= 1ull << s; d.pushed_edges += (double)mf_s[s]; }
   }
+  if (batch_decide_finish(d.qmask, d.pmask, r, open_u)) { d.qmask |= d.pmask; d.pmask = 0; d.pushed_edges = 0; }
   d.kind = batch_decide_kind(d.qmask, d.pmask, d.pushed_edges, r, iteration_left);
   d.stash = batch_decide_stash(d.pmask, d.pushed_edges, r.n, d.kind);
   return d;

@@ -43,8 +43,9 @@ constexpr int kBatchPushSlice = 1024; // push: out-edge slices (every edge is a 
 constexpr int kBatchSerial = 4;       // serial probes per lane before the wave takes over
 constexpr int kBatchSlots = 16;       // counter slots (spreads same-address atomics)
 constexpr int kBatchStoreMax = 16;    // level words kept for the final label pass
-constexpr int kBatchCounters = 2 + 128 + 1;   // per slot: vertices, the big in-rows still open (below), {nf_s, mf_s} per source, big out-rows found
-constexpr int kCntInOpen = 1, kCntBigOut = 2 + 128;
+constexpr int kBatchCounters = 2 + 128 + 2;   // per slot: vertices, the big in-rows still open (below), {nf_s, mf_s} per source, big out-rows found, U (below)
+constexpr int kCntInOpen = 1, kCntBigOut = 2 + 128, kCntOpenU = 2 + 128 + 1;
+static_assert(kBatchCounters <= kBlock, "batch_totals_kernel sums a counter per thread");
 constexpr int kBatchBoxPer = kBatchCounters + 9;      // the host's box: where the light-level launch leaves TailState::cum and ::last
 constexpr int kBoxDecision = kBatchCounters + 5;      // box: {qmask, pmask, kind, stash} of the NEXT level, as batch_totals_kernel decided it
 constexpr int kBatchCtlWords = 5;                     // the device's copy of the first three, behind the counter slots; [3]: the last light-level launch's status; [4]: stash
@@ -60,6 +61,12 @@ constexpr size_t kListHeader = (size_t)kListSegs * kListLenStride * sizeof(unsig
 // bit 62 set when the level's batch_big_apply_kernel counted them at all; counter kCntBigOut: the vertices with a new bit
 // whose out-row is big
 constexpr unsigned long long kInOpenCounted = 1ull << 62;
+// counter kCntOpenU: U, the in-edges of the rows a level's pull leaves open -- a row that still lacks a bit of some source
+// in qmask adds its whole in-degree (batch_pull_kernel for the rows it finishes itself, batch_big_apply_kernel for the
+// rows of the slice kernels).  It bounds what the next level's pull can inspect for those sources.  It is COMPLETE only
+// when the level pulled every live source (pmask = 0, qmask != 0): batch_totals_kernel then publishes it with bit 62 set,
+// and only then may the finishing rule (batch_decide.hpp) read it.  At most nvals, far below 2^62.
+constexpr unsigned long long kOpenUComplete = 1ull << 62;
 constexpr int kBatchBoxWords = kBatchBoxPer + 128 + 64;
 
 typedef unsigned long long u64;
@@ -136,6 +143,7 @@ struct WaveTotals {
   u64 nf = 0, mf = 0;
   unsigned int verts = 0;             // wave-uniform: vertices with any new bit
   unsigned int bigs = 0;              // wave-uniform: those of them whose out-row is big (the next level's push has slices to expand)
+  u64 open_in = 0;                    // per lane: the in-degrees of the rows this lane's pull left open (counter kCntOpenU); only the pull kernels add to it
 };
 
 // accounting (and, beyond the stored levels, labels) of a lane's new bits; wave-collective.  The 64 x 64 bit
@@ -195,19 +203,24 @@ __device__ inline void totals_init(BatchTotals* lds) {
   for (int i = threadIdx.x; i < kBatchCounters; i += blockDim.x) lds->v[i] = 0;
   __syncthreads();
 }
-__device__ inline void totals_flush_to(u64* slots, BatchTotals* lds, const WaveTotals& acc) {
+// (with_open: the two pull kernels that count U; a literal at every call, so nobody else pays for the wave sum)
+__device__ inline void totals_flush_to(u64* slots, BatchTotals* lds, const WaveTotals& acc, bool with_open = false) {
   const int lane = lane_id();
   if (acc.nf) atomicAdd(&lds->v[2 + 2 * lane], acc.nf);
   if (acc.mf) atomicAdd(&lds->v[3 + 2 * lane], acc.mf);
   if (lane == 0 && acc.verts) atomicAdd(&lds->v[0], (u64)acc.verts);
   if (lane == 0 && acc.bigs) atomicAdd(&lds->v[kCntBigOut], (u64)acc.bigs);
+  if (with_open) {
+    const u64 open_in = wave_sum_u64(acc.open_in);          // one LDS update per wave, one per workgroup and slot below: no atomic per row
+    if (lane == 0 && open_in) atomicAdd(&lds->v[kCntOpenU], open_in);
+  }
   __syncthreads();
   u64* dst = slots + (size_t)(blockIdx.x & (kBatchSlots - 1)) * kBatchCounters;
   for (int i = threadIdx.x; i < kBatchCounters; i += blockDim.x)
     if (lds->v[i]) atomicAdd(&dst[i], lds->v[i]);
 }
-__device__ inline void totals_flush(const BatchArgs& a, BatchTotals* lds, const WaveTotals& acc) {
-  totals_flush_to(a.counters, lds, acc);
+__device__ inline void totals_flush(const BatchArgs& a, BatchTotals* lds, const WaveTotals& acc, bool with_open = false) {
+  totals_flush_to(a.counters, lds, acc, with_open);
 }
 
 // the wave scans entries [rs, re) of `ind`, ORs word[ind[q]] and stops once `nd` is covered
@@ -315,7 +328,8 @@ __global__ __launch_bounds__(kBlock) void batch_pull_kernel(BatchArgs a) {
     u64 need = ~seen & qmask;
     Index p = 0, e = 0;
     if (need) { p = a.iptr[v]; e = a.iptr[v + 1]; }
-    const bool big = e - p >= a.big;                       // probed here, finished by the slice kernels
+    const Index indeg = e - p;
+    const bool big = indeg >= a.big;                       // probed here, finished by the slice kernels
     if (p == e) need = 0;
     if (__ballot(need != 0) == 0ull) {
       if (valid) a.fnext[v] = seen & stash;
@@ -379,9 +393,10 @@ inc = (Index)wave_incl_scan_u32((unsigned)inc);
       a.fnext[v] = newb | (seen & stash);                  // a big row's probe result: the slices add to it,
       if (newb && !big) a.seen[v] = seen | newb;           // batch_big_apply_kernel claims and counts it
     }
+    if (!big && (need & ~newb)) tot.open_in += (u64)indeg;  // left open: the row's in-edges are part of U (a big row's: batch_big_apply_kernel)
     batch_commit(a, tot, valid ? v : 0, big ? 0ull : newb);
   }
-  totals_flush(a, &lds, tot);
+  totals_flush(a, &lds, tot, true);
 }
 
 // pull, big rows: a wave per 4096-entry slice
@@ -420,6 +435,7 @@ __global__ __launch_bounds__(kBlock) void batch_big_apply_kernel(BatchArgs a) {
       newb = a.fnext[v] & ~seen & qmask;
       if (newb) a.seen[v] = seen | newb;
       left = ~(seen | newb) & all;
+      if (left & qmask) tot.open_in += (u64)(a.iptr[v + 1] - a.iptr[v]);   // this level's pull leaves it open: its share of U
     }
     open += (unsigned int)__popcll(__ballot(left != 0ull));
     batch_commit(a, tot, v, newb);
@@ -428,7 +444,7 @@ __global__ __launch_bounds__(kBlock) void batch_big_apply_kernel(BatchArgs a) {
     const u64 add = (u64)open + (blockIdx.x == 0 && threadIdx.x == 0 ? kInOpenCounted : 0ull);
     if (add) atomicAdd(&lds.v[kCntInOpen], add);
   }
-  totals_flush(a, &lds, tot);
+  totals_flush(a, &lds, tot, true);
 }
 
 // N out-edge slots of frontier vertices (entry q[j] < 0 = empty) carrying the pushed bits fw[j]: the dependent
@@ -742,20 +758,28 @@ __global__ __launch_bounds__(kBlock) void batch_labels_kernel(LabelArgs a) {
 //
 // ... and the NEXT level decided here, from the totals just summed, by the rule the host uses (batch_decide.hpp): a lane
 // per source.  The decision goes to the control block behind the counters, where pull kernels launched ahead of the
-// host find it, and into the box, where the host reads it: one authority, nobody computes it a second time.
+// host find it, and into the box, where the host reads it: one authority, nobody computes it a second time.  The
+// finishing rule is applied here and nowhere else in a running sweep: lane 0 has both masks and the level's U, which
+// the host marks complete when the level pulled every live source.
 struct DecideArgs {
   BatchRule rule;
   int iteration_left;                 // the level decided on may run at all
+  int open_complete;                  // the level just run pulled every live source (pmask = 0, qmask != 0): its U is complete.  The host
+                                      // knows the level's masks whoever decided them -- it read them from the box
   u64* ctl;
 };
 __global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64* box, u64 seq, DecideArgs d) {
-  __shared__ u64 s_nf[64], s_mf[64];
+  __shared__ u64 s_nf[64], s_mf[64], s_open;
   const int i = threadIdx.x;
   if (i < kBatchCounters) {
     u64 t = 0;
     for (int slot = 0; slot < kBatchSlots; ++slot) {
       t += counters[slot * kBatchCounters + i];
       counters[slot * kBatchCounters + i] = 0ull;
+    }
+    if (i == kCntOpenU) {
+      s_open = t;
+      if (d.open_complete) t |= kOpenUComplete;
     }
     __hip_atomic_store(&box[i], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (i >= 2 && i < 2 + 128) ((i & 1) ? s_mf : s_nf)[(i - 2) >> 1] = t;
@@ -764,9 +788,12 @@ __global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64
   if (i < kWave) {
     const u64 under = __ballot(batch_decide_under(s_nf, i, d.rule));
     const int way = batch_decide_source(s_nf, s_mf, i, d.rule, under);
-    const u64 q = __ballot(way == 2), p = __ballot(way == 1);
-    const u64 pushed = wave_sum_u64(way == 1 ? s_mf[i] : 0ull);   // integers below 2^53: the host's sum of doubles is the same number
+    u64 q = __ballot(way == 2), p = __ballot(way == 1);
+    u64 pushed = wave_sum_u64(way == 1 ? s_mf[i] : 0ull);   // integers below 2^53: the host's sum of doubles is the same number
     if (i == 0) {
+      // the finishing rule: few in-edges left open by a level that pulled everybody -- the sources the base rule would
+      // push are pulled with the rest, and the level has no push stage
+      if (batch_decide_finish(q, p, d.rule, d.open_complete ? (long long)s_open : kOpenUnknown)) { q |= p; p = 0; pushed = 0; }
       const u64 kind = (u64)batch_decide_kind(q, p, (double)pushed, d.rule, d.iteration_left != 0);
       const u64 stash = batch_decide_stash(p, (double)pushed, d.rule.n, (int)kind);
       d.ctl[0] = q; d.ctl[1] = p; d.ctl[2] = kind; d.ctl[kCtlStash] = stash;
@@ -1500,10 +1527,27 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   // plus an atomic on it, about 50 G edges/s on RMAT-22 against 85 G/s for a pulled entry), then the heaviest of them
   // are pulled as well.  The host decides the sweep's first level and the one after a light-level launch; after a level
   // of this loop the totals kernel has decided the next one on the device, and that decision is the one used.
+  // ---- the finishing rule.  At a sweep's end a source is under the switch point because almost nothing is left for it to
+  // find, and pushing it costs what a push stage costs whatever it pushes: batch_push_kernel reads all n frontier words to
+  // find the few that carry a pushed bit, batch_push_commit_kernel reads all n words again to count what arrived (26 us a
+  // level on RMAT-22, 41 with the slice kernel, for 60-125 K edges) -- while the same level pulls other sources over all n
+  // rows anyway.  The pull kernels count U, the in-edges of the rows they leave open (counter kCntOpenU): after a level
+  // that pulled every live source U bounds what the next pull can inspect, for all sources.  When the per-source rule
+  // would pull some sources and push others and U <= finish_limit * nvals (GRB_BATCH_FINISH_LIMIT, 0.01), the pushed
+  // sources are pulled too and the level has no push stage (batch_decide_finish).  Only the totals kernel ever has a
+  // complete U: the levels the host decides (the first, the one after a light-level launch) keep the per-source rule, as
+  // does a level after one that pushed anything or a level that pulls nobody.  GRB_BATCH_FINISH=0: no such rule.
+  static const double finish_limit = [] {
+    const char* on = getenv("GRB_BATCH_FINISH");
+    if (on && atoi(on) == 0) return -1.0;
+    const char* e = getenv("GRB_BATCH_FINISH_LIMIT");
+    return e ? atof(e) : 0.01;
+  }();
   BatchRule rule;
   rule.k = k; rule.n = (long long)n; rule.nvals = (long long)A->nvals;
   rule.mode = mode == GRB_PULLONLY ? kDecidePullOnly : mode == GRB_PUSHONLY ? kDecidePushOnly : kDecidePushPull;
   rule.switchpoint = switchpoint; rule.budget = budget; rule.tail_limit = tail_on ? tail_edges : 0.0;
+  rule.finish_limit = finish_limit;
   // Launching ahead: behind a level's totals kernel the NEXT level's pull kernels are enqueued at once, before the host
   // has the totals -- they take their bits from the control block the totals kernel leaves, and return at once when that
   // level is no level of this loop.  The GPU then pulls while the host turns the level round.  Stream order is all this
@@ -1761,11 +1805,15 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       }
       hipLaunchKernelGGL(batch_push_commit_kernel, dim3(grid), dim3(kBlock), 0, st, a);
       GRB_HIP_TRY(hipGetLastError());
+      if (trace)
+        fprintf(stderr, "batch push stage of level %d: batch_push_kernel, %sbatch_push_commit_kernel\n", iter,
+                owners ? "range owners, " : big_rows ? "batch_push_slices_kernel, " : "");
     }
     // the totals come back through a pinned, host-coherent box the host polls: no copy, no stream wait
     DecideArgs da;
     da.rule = rule;
     da.iteration_left = iter + 1 <= max_niter ? 1 : 0;
+    da.open_complete = P == 0 && Q != 0 ? 1 : 0;            // every live source pulled: the level's U covers them all
     da.ctl = d_ctl;
     hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, d_box, ++box_seq, da);
     GRB_HIP_TRY(hipGetLastError());
@@ -1811,11 +1859,11 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     }
     if (trace)
       fprintf(stderr, "batch level %d: pull %d sources, push %d (%.0f edges, %s) -> vertices %llu pairs %llu, big in-rows open %s%llu, "
-              "big out-rows found %lld, next level %s  %.1f us\n",
+              "big out-rows found %lld, next level %s  %.1f us, U %llu%s\n",
               iter, __builtin_popcountll(Q), __builtin_popcountll(P), pushed_edges, a.claims ? "claims" : "direct", t[0],
               pairs, (t[kCntInOpen] & kInOpenCounted) ? "" : "(not counted) ", t[kCntInOpen] & (kInOpenCounted - 1), big_out_new,
               dec.kind == kDecideHost ? (pulled_ahead ? "pulled ahead" : "host") : dec.kind == kDecideLight ? "light" : "none",
-              now_us() - t_lvl);
+              now_us() - t_lvl, t[kCntOpenU] & (kOpenUComplete - 1), (t[kCntOpenU] & kOpenUComplete) ? "" : " (not complete)");
     dec.pushed_edges = 0;
     for (int s = 0; s < k; ++s) if ((dec.pmask >> s) & 1ull) dec.pushed_edges += (double)mf_s[s];
     if (!any_left) break;
