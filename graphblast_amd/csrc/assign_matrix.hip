@@ -18,7 +18,8 @@
 //                                         column array at all under a null J) with the constant
 //   bins      rows not in I, and rows whose T side is empty under an accum, keep what they hold whatever the mask says:
 //             they are counted by their pointers and copied entry by entry (one balanced pass over the old C's entries,
-//             an entry finding its row by binary search).  The others by merged length |old C row| + |T row|:
+//             an entry finding its row by binary search).  The others by merged length |old C row| + |T row|
+//             (the shared pipeline of row_bins.hpp):
 //               short  len <= 2 * kAShort   a 16-lane group per row (four rows per wave)
 //               wave   len <= kASeg         a wave per row
 //               hub    the rest             segments of kASeg merged positions, a wave each, cut at merge-path splits
@@ -29,7 +30,7 @@
 //             Kept flags are balloted into slots.  A symbolic pass counts, the 64-bit total is checked against INT32_MAX,
 //             a numeric pass writes.  No atomics on values.
 // C's CSC is the same routine over the other orientations with I and J exchanged.
-#include "common.hpp"
+#include "row_bins.hpp"
 
 namespace grb {
 
@@ -47,10 +48,6 @@ struct AmT {
   const Index* cptr;                    // the inverse of the column list: c is in the region when cptr[c + 1] > cptr[c];
 };                                      // nullptr: every column is
 
-__device__ inline void am_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 __device__ inline unsigned int am_tcol(const AmT& t, Index p) { return (unsigned int)(t.ind ? t.ind[p] : p); }
 template <typename T> __device__ inline T am_from(unsigned int b);
 template <> __device__ inline float am_from<float>(unsigned int b) { return __uint_as_float(b); }
@@ -63,8 +60,16 @@ __device__ inline bool am_is_copy(const AmT& t, Index r, int accum) {
   const Index b = t.beg[r];
   return b < 0 || (accum >= 0 && t.end[r] == b);
 }
-// -1 none (empty), 0 short, 1 wave, 2 hub
-__device__ inline int am_bin_of(long long len) { return len <= 0 ? -1 : len <= 2 * kAShort ? 0 : len <= kASeg ? 1 : 2; }
+// a row's merged length for the bins; the copied rows are in none
+struct AmRowLen {
+  const Index* a_ptr;
+  AmT t;
+  int accum;
+  __device__ long long operator()(long long r) const {
+    if (am_is_copy(t, (Index)r, accum)) return 0;
+    return (long long)(a_ptr[r + 1] - a_ptr[r]) + (t.end[r] - t.beg[r]);
+  }
+};
 
 // ---- lists
 __global__ __launch_bounds__(kBlock) void am_dup_kernel(const Index* __restrict__ jptr, Index dim, unsigned int* __restrict__ flag) {
@@ -156,84 +161,22 @@ __global__ __launch_bounds__(kBlock) void am_unpack_kernel(const unsigned long l
   for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < n; p += stride) ind[p] = (Index)(unsigned int)keys[p];
 }
 
-// ---- bins.  tot[0 .. 3]: short rows, wave rows, hub segments, entries of the copied rows.  The copied rows' counts are
-// their lengths, written here.
-__global__ __launch_bounds__(kBlock) void am_len_kernel(const Index* __restrict__ a_ptr, AmT t, Index m, int accum,
-                                                        unsigned int* __restrict__ counts, unsigned long long* __restrict__ tot) {
-  unsigned int n_short = 0, n_wave = 0;
-  unsigned long long n_seg = 0, n_copy = 0;
+// ---- bins.  tot[0 .. 3] (row_bins.hpp): short rows, wave rows, hub segments, entries of the copied rows.  The copied rows'
+// counts are their lengths, written here; row_bin_kernel then fills lists that hold exactly what was counted here.
+__global__ __launch_bounds__(kBlock) void am_len_kernel(AmRowLen len_of, Index m, unsigned int* __restrict__ counts,
+                                                        unsigned long long* __restrict__ tot) {
+  RowLenSums sums;
   const long long stride = (long long)gridDim.x * kBlock;
   for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < m; r += stride) {
-    const Index la = a_ptr[r + 1] - a_ptr[r];
-    if (am_is_copy(t, (Index)r, accum)) {
+    if (am_is_copy(len_of.t, (Index)r, len_of.accum)) {
+      const Index la = len_of.a_ptr[r + 1] - len_of.a_ptr[r];
       counts[r] = (unsigned int)la;
-      n_copy += (unsigned long long)la;
+      sums.n_own += (unsigned long long)la;
       continue;
     }
-    const long long len = (long long)la + (t.end[r] - t.beg[r]);
-    const int bin = am_bin_of(len);
-    n_short += bin == 0;
-    n_wave += bin == 1;
-    if (bin == 2) n_seg += (unsigned long long)((len + kASeg - 1) / kASeg);
+    row_len_add<2 * kAShort, kASeg>(sums, len_of(r));
   }
-  n_short = wave_sum_u32(n_short);
-  n_wave = wave_sum_u32(n_wave);
-  n_seg = wave_sum_u64(n_seg);
-  n_copy = wave_sum_u64(n_copy);
-  if (lane_id() == 0) {
-    if (n_short) atomicAdd(&tot[0], (unsigned long long)n_short);
-    if (n_wave) atomicAdd(&tot[1], (unsigned long long)n_wave);
-    if (n_seg) atomicAdd(&tot[2], n_seg);
-    if (n_copy) atomicAdd(&tot[3], n_copy);
-  }
-}
-
-// rows -> bin lists, as ewm_bin_kernel: a workgroup bins kABinTile consecutive rows into LDS lists and appends each with
-// one global atomic; a hub row takes its consecutive segment slots.  The lists hold exactly what am_len_kernel counted.
-constexpr int kABinTile = kBlock * 8;
-__global__ __launch_bounds__(kBlock) void am_bin_kernel(const Index* __restrict__ a_ptr, AmT t, Index m, int accum,
-                                                        Index* __restrict__ l_short, Index* __restrict__ l_wave,
-                                                        Index* __restrict__ seg_row, Index* __restrict__ seg_k,
-                                                        unsigned int* __restrict__ ctr) {
-  __shared__ Index s_list[2][kABinTile];
-  __shared__ unsigned int s_cnt[2], s_base[2];
-  const int lane = lane_id();
-  for (long long tile = (long long)blockIdx.x * kABinTile; tile < m; tile += (long long)gridDim.x * kABinTile) {
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (int x = threadIdx.x - lane; x < kABinTile; x += kBlock) {   // wave-uniform: x is the wave's first row of the step
-      const long long r = tile + x + lane;
-      int bin = -1;
-      long long len = 0;
-      if (r < m && !am_is_copy(t, (Index)r, accum)) {
-        len = (long long)(a_ptr[r + 1] - a_ptr[r]) + (t.end[r] - t.beg[r]);
-        bin = am_bin_of(len);
-      }
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const unsigned long long mask = __ballot(bin == b);
-        if (!mask) continue;
-        const int leader = __ffsll((long long)mask) - 1;
-        unsigned int at = 0;
-        if (lane == leader) at = atomicAdd(&s_cnt[b], (unsigned int)__popcll(mask));
-        at = (unsigned int)__shfl((int)at, leader, kWave);
-        if (bin == b) s_list[b][at + __popcll(mask & ((1ull << lane) - 1ull))] = (Index)r;
-      }
-      if (bin == 2) {
-        const Index nseg = (Index)((len + kASeg - 1) / kASeg);
-        const unsigned int at = atomicAdd(&ctr[2], (unsigned int)nseg);
-        for (Index k = 0; k < nseg; ++k) { seg_row[at + k] = (Index)r; seg_k[at + k] = k; }
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) s_base[threadIdx.x] = s_cnt[threadIdx.x] ? atomicAdd(&ctr[threadIdx.x], s_cnt[threadIdx.x]) : 0u;
-    __syncthreads();
-    for (int b = 0; b < 2; ++b) {
-      Index* out = (b == 0 ? l_short : l_wave) + s_base[b];
-      for (unsigned int j = threadIdx.x; j < s_cnt[b]; j += kBlock) out[j] = s_list[b][j];
-    }
-    __syncthreads();
-  }
+  row_len_totals(sums, tot);
 }
 
 // ---- the merge.  One kernel for every bin: groups of G lanes (kAShort or kWave), an item each -- a whole row (seg_k ==
@@ -296,7 +239,7 @@ __global__ __launch_bounds__(kBlock) void am_merge_kernel(const Index* __restric
       }
       s_a[g0 + t] = av;
       s_b[g0 + t] = bv;
-      am_wave_sync();
+      wave_lds_sync();
       int rb = 0, ra = 0;                              // # B window < av, # A window <= bv
 #pragma unroll
       for (int s = G / 2; s > 0; s >>= 1) {
@@ -313,7 +256,7 @@ __global__ __launch_bounds__(kBlock) void am_merge_kernel(const Index* __restric
       if constexpr (kNum) partner = (unsigned int)__shfl((int)bval, (lane & ~(G - 1)) + (rb & (G - 1)), kWave);
       const int n_a = __popcll(__ballot(in_a) & gmask);
       const unsigned int last_a = n_a > 0 ? s_a[g0 + n_a - 1] : prev_a;
-      am_wave_sync();
+      wave_lds_sync();
       if (in_a) {
         s_col[g0 + t + rb] = av;
         s_kind[g0 + t + rb] = pair_a ? 1 : 0;
@@ -327,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void am_merge_kernel(const Index* __restric
         s_kind[g0 + t + ra] = 2;
         if constexpr (kNum) s_z[g0 + t + ra] = bval;
       }
-      am_wave_sync();
+      wave_lds_sync();
       const unsigned int col = t < lim ? s_col[g0 + t] : kANone;
       const int kind = s_kind[g0 + t];
       bool keep = col != kANone, use_z = true;
@@ -364,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void am_merge_kernel(const Index* __restric
       j0 += lim - n_a;
       prev_a = last_a;
       d += lim;
-      am_wave_sync();
+      wave_lds_sync();
     }
     if constexpr (!kNum) {
       if (t == 0) {
@@ -397,27 +340,7 @@ __global__ __launch_bounds__(kBlock) void am_copy_kernel(const Index* __restrict
   }
 }
 
-// the rows' counts in 64 bits (the u32 scan wraps above 2^32)
-__global__ __launch_bounds__(kBlock) void am_total_kernel(const unsigned int* __restrict__ counts, Index m,
-                                                          unsigned long long* __restrict__ total) {
-  unsigned long long acc = 0;
-  const long long stride = (long long)gridDim.x * kBlock;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < m; i += stride) acc += counts[i];
-  acc = wave_sum_u64(acc);
-  if (lane_id() == 0 && acc) atomicAdd(total, acc);
-}
-
 namespace {
-
-inline int am_grid(long long items, int per_block) {
-  const long long b = (items + per_block - 1) / per_block;
-  return b > 16384 ? 16384 : (int)(b < 1 ? 1 : b);
-}
-inline int am_bits_of(Index dim) {
-  int b = 1;
-  while (b < 31 && ((long long)1 << b) < (long long)dim) ++b;
-  return b;
-}
 
 // T of one orientation and the device memory behind it
 struct TBuf {
@@ -455,7 +378,7 @@ grb_info t_from_pairs(TBuf* b, Index n, Index m, Index ncols, const IndexList* R
   const size_t cap = (size_t)(n > 0 ? n : 1);
   unsigned long long* keys = (unsigned long long*)b->pairs.p;
   unsigned int* pay = (unsigned int*)(keys + cap);
-  GRB_TRY(device_sort_pairs(keys, pay, n, am_bits_of(ncols), am_bits_of(m)));
+  GRB_TRY(device_sort_pairs(keys, pay, n, index_bits(ncols), index_bits(m)));
   GRB_TRY(ewm_alloc(&b->ind, 4 * cap));
   GRB_TRY(t_alloc_range(b, m));
   if (n > 0) {
@@ -549,105 +472,54 @@ grb_info t_constant(unsigned int cbits, IndexList* R, IndexList* Cl, Index m, TB
 }
 
 template <typename T, bool kNum>
-grb_info launch_merge(hipStream_t s, const unsigned int* nbin, const Index* l_short, const Index* l_wave, const Index* seg_row,
-                      const Index* seg_k, const CsrArrays& X, const AmT& t, const CsrArrays* M, int mask_f32, int scmp, int accum,
-                      unsigned int* counts, unsigned int* seg_cnt, const Index* c_ptr, Index* c_ind, unsigned int* c_val) {
+grb_info launch_merge(hipStream_t s, const RowBins& b, const CsrArrays& X, const AmT& t, const CsrArrays* M, int mask_f32, int scmp,
+                      int accum, unsigned int* counts, const Index* c_ptr, Index* c_ind, unsigned int* c_val) {
   const Index* mp = M ? M->ptr : nullptr;
   const Index* mi = M ? M->ind : nullptr;
   const void* mv = M ? M->val : nullptr;
-  const unsigned int* xv = (const unsigned int*)X.val;
-  if (nbin[0])
-    hipLaunchKernelGGL((am_merge_kernel<T, kAShort, kNum>), dim3(am_grid(nbin[0], kBlock / kAShort)), dim3(kBlock), 0, s, l_short, nullptr,
-                       (Index)nbin[0], X.ptr, X.ind, xv, t, mp, mi, mv, mask_f32, scmp, accum, counts, nullptr, c_ptr, nullptr, c_ind,
-                       c_val);
-  if (nbin[1])
-    hipLaunchKernelGGL((am_merge_kernel<T, kWave, kNum>), dim3(am_grid(nbin[1], kWavesPerBlock)), dim3(kBlock), 0, s, l_wave, nullptr,
-                       (Index)nbin[1], X.ptr, X.ind, xv, t, mp, mi, mv, mask_f32, scmp, accum, counts, nullptr, c_ptr, nullptr, c_ind,
-                       c_val);
-  if (nbin[2])
-    hipLaunchKernelGGL((am_merge_kernel<T, kWave, kNum>), dim3(am_grid(nbin[2], kWavesPerBlock)), dim3(kBlock), 0, s, seg_row, seg_k,
-                       (Index)nbin[2], X.ptr, X.ind, xv, t, mp, mi, mv, mask_f32, scmp, accum, counts, seg_cnt, c_ptr, seg_cnt, c_ind,
-                       c_val);
-  GRB_HIP_TRY(hipGetLastError());
-  return GRB_SUCCESS;
+  return for_each_bin<kAShort>(b, [&](auto g, int grid, const Index* items, const Index* seg_k, Index n) {
+    unsigned int* seg_cnt = seg_k ? b.seg_cnt : nullptr;   // a segment's count (kNum = false), then its offset
+    hipLaunchKernelGGL((am_merge_kernel<T, decltype(g)::value, kNum>), dim3(grid), dim3(kBlock), 0, s, items, seg_k, n, X.ptr, X.ind,
+                       (const unsigned int*)X.val, t, mp, mi, mv, mask_f32, scmp, accum, counts, seg_cnt, c_ptr, seg_cnt, c_ind, c_val);
+  });
 }
 
 // one orientation: the m rows of the old C (X) merged with T under the mask's rows (M, nullable) -> out
 grb_info assign_side(int dtype, const CsrArrays& X, Index m, const AmT& t, const CsrArrays* M, int mask_f32, int scmp, int accum,
                      Side* out) {
   hipStream_t s = ctx().stream;
+  const AmRowLen len_of{X.ptr, t, accum};
   GRB_TRY(ewm_alloc(&out->ptr, 4 * ((size_t)m + 1)));
   unsigned int* counts = (unsigned int*)out->ptr.p;
   GRB_HIP_TRY(hipMemsetAsync(counts, 0, 4 * ((size_t)m + 1), s));
-  EwmBuf head;                                           // [4] 64-bit sizes, [3] list cursors, the 64-bit total
-  GRB_TRY(ewm_alloc(&head, 64));
-  GRB_HIP_TRY(hipMemsetAsync(head.p, 0, 64, s));
-  unsigned long long* d_tot = (unsigned long long*)head.p;
-  unsigned int* d_ctr = (unsigned int*)(d_tot + 4);
-  unsigned long long* d_total = d_tot + 6;
-  unsigned long long tot[4] = {0, 0, 0, 0};
+  RowBins b;
+  GRB_TRY(row_bins_head(&b, s));
   if (m > 0) {
-    hipLaunchKernelGGL(am_len_kernel, dim3(stream_grid(m, kBlock * 8)), dim3(kBlock), 0, s, X.ptr, t, m, accum, counts, d_tot);
-    GRB_HIP_TRY(hipGetLastError());
-    GRB_HIP_TRY(hipMemcpyAsync(tot, d_tot, 32, hipMemcpyDeviceToHost, s));
-    GRB_HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (tot[2] > (unsigned long long)INT32_MAX) return GRB_OUT_OF_MEMORY;   // (more than 2^42 merged positions to visit)
-  const unsigned int nbin[3] = {(unsigned int)tot[0], (unsigned int)tot[1], (unsigned int)tot[2]};
-  const size_t nseg = nbin[2];
-  const size_t scan_len = ((size_t)m > nseg ? (size_t)m : nseg) + 1;
-  EwmBuf work;
-  GRB_TRY(ewm_alloc(&work, 4 * ((size_t)nbin[0] + nbin[1] + 3 * nseg + 1) + device_scan_u32_scratch((long long)scan_len)));
-  Index* l_short = (Index*)work.p;
-  Index* l_wave = l_short + nbin[0];
-  Index* seg_row = l_wave + nbin[1];
-  Index* seg_k = seg_row + nseg;
-  unsigned int* seg_cnt = (unsigned int*)(seg_k + nseg);
-  unsigned int* scan = seg_cnt + nseg + 1;
-  if (m > 0 && (nbin[0] || nbin[1] || nbin[2])) {
-    hipLaunchKernelGGL(am_bin_kernel, dim3(stream_grid(m, kABinTile)), dim3(kBlock), 0, s, X.ptr, t, m, accum, l_short, l_wave, seg_row,
-                       seg_k, d_ctr);
+    hipLaunchKernelGGL(am_len_kernel, dim3(stream_grid(m, kBlock * 8)), dim3(kBlock), 0, s, len_of, m, counts, b.d_tot);
     GRB_HIP_TRY(hipGetLastError());
   }
-  GRB_HIP_TRY(hipMemsetAsync(seg_cnt, 0, 4 * (nseg + 1), s));
+  GRB_TRY(row_bins_sized(&b, m, s));
+  if (m > 0 && (b.nbin[0] || b.nbin[1] || b.nbin[2])) GRB_TRY((row_bins_fill<2 * kAShort, kASeg>(b, len_of, m, s)));
   // ---- symbolic (value-free: one instantiation serves both types)
-  GRB_TRY((launch_merge<float, false>(s, nbin, l_short, l_wave, seg_row, seg_k, X, t, M, mask_f32, scmp, accum, counts, seg_cnt, nullptr,
-                                      nullptr, nullptr)));
-  unsigned long long total = 0;
-  if (m > 0) {
-    hipLaunchKernelGGL(am_total_kernel, dim3(stream_grid(m, kBlock * 8)), dim3(kBlock), 0, s, counts, m, d_total);
-    GRB_HIP_TRY(hipGetLastError());
-    GRB_HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
-    GRB_HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (total > (unsigned long long)INT32_MAX) return GRB_OUT_OF_MEMORY;   // grb_index is 32 bits; C keeps what it held
-  out->nnz = (Index)total;
-  GRB_TRY(device_exclusive_scan_u32_in(counts, (long long)m + 1, scan));   // counts -> row pointers
-  if (nseg) GRB_TRY(device_exclusive_scan_u32_in(seg_cnt, (long long)nseg + 1, scan));   // hub segments' offsets
-  out->h_ptr.resize((size_t)m + 1);
-  GRB_HIP_TRY(hipMemcpy(out->h_ptr.data(), counts, 4 * ((size_t)m + 1), hipMemcpyDeviceToHost));
-  const size_t cap = (size_t)(out->nnz > 0 ? out->nnz : 1);
-  GRB_TRY(ewm_alloc(&out->ind, 4 * cap));
-  GRB_TRY(ewm_alloc(&out->val, 4 * cap));
+  GRB_TRY((launch_merge<float, false>(s, b, X, t, M, mask_f32, scmp, accum, counts, nullptr, nullptr, nullptr)));
+  GRB_TRY(row_bins_total(b, counts, m, false, s, out));  // (the merge kernel has added the hub segments into their rows)
+  GRB_TRY(row_bins_pointers(b, m, out));
   if (out->nnz == 0) return GRB_SUCCESS;
   // ---- numeric
   const Index* cp = (const Index*)counts;
   Index* ci = (Index*)out->ind.p;
   unsigned int* cv = (unsigned int*)out->val.p;
-  if (tot[3] > 0) {
+  if (b.own > 0) {                                       // the copied rows' entries
     hipLaunchKernelGGL(am_copy_kernel, dim3(stream_grid(X.nvals, kBlock)), dim3(kBlock), 0, s, X.ptr, X.ind, (const unsigned int*)X.val, m,
                        X.nvals, t, accum, cp, ci, cv);
     GRB_HIP_TRY(hipGetLastError());
   }
-  if (dtype == GRB_F32)
-    GRB_TRY((launch_merge<float, true>(s, nbin, l_short, l_wave, seg_row, seg_k, X, t, M, mask_f32, scmp, accum, nullptr, seg_cnt, cp, ci,
-                                       cv)));
-  else
-    GRB_TRY((launch_merge<int, true>(s, nbin, l_short, l_wave, seg_row, seg_k, X, t, M, mask_f32, scmp, accum, nullptr, seg_cnt, cp, ci,
-                                     cv)));
+  if (dtype == GRB_F32) GRB_TRY((launch_merge<float, true>(s, b, X, t, M, mask_f32, scmp, accum, nullptr, cp, ci, cv)));
+  else GRB_TRY((launch_merge<int, true>(s, b, X, t, M, mask_f32, scmp, accum, nullptr, cp, ci, cv)));
   GRB_HIP_TRY(hipStreamSynchronize(s));                  // (the lists are freed on the way out)
   return GRB_SUCCESS;
 }
+
 
 // what every form checks first, and the old C's two orientations (an unbuilt C is an empty matrix)
 struct OldC {

@@ -493,6 +493,15 @@ __device__ inline bool mask_pass(const void* mask, int mask_f32, int scmp, Index
   return mask_nonzero(mask, mask_f32, i) != (scmp != 0);
 }
 
+// the first position in [lo, hi) whose index is >= x (hi if none): indices ascend
+__device__ __forceinline__ Index index_lower_bound(const Index* __restrict__ a, Index lo, Index hi, Index x) {
+  while (lo < hi) {
+    const Index mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 // Grid for grid-stride kernels: enough workgroups to fill 256 CUs x 8, never zero.
 inline int stream_grid(long long work_items, int per_block = kBlock) {

@@ -3,7 +3,8 @@
 // GrB_NOT_IMPLEMENTED, backend/cuda/operations.hpp:414-423) and the transposition (grb_transpose, operations.hpp:682).
 //
 // Element-wise: row i of C is the merge of row i of op(A) and row i of op(B) (two ascending column lists), filtered by
-// row i of the mask, in a symbolic pass (counts) and a numeric pass (columns and values) over the same row bins:
+// row i of the mask, in a symbolic pass (counts) and a numeric pass (columns and values) over the same row bins (the bin
+// kernel, the launches per bin and the counts-to-pointers tail: row_bins.hpp):
 //   bins      len(i) = |row i of op(A)| + |row i of op(B)| (rows of length 0, and for the intersection rows with an empty
 //             side, are in no bin: their count stays 0)
 //               short  len <= 2 * kShort          a 16-lane group per row (four rows per wave)
@@ -26,7 +27,7 @@
 // order by the stable radix sort of build.hip (key = the column, entries in row-major order: rows stay ascending inside
 // every column), the row and value of every entry gathered behind it, and every column's start found by binary search
 // in the sorted keys.
-#include "common.hpp"
+#include "row_bins.hpp"
 
 namespace grb {
 
@@ -34,68 +35,16 @@ constexpr int kShort = 16;              // lanes per row of the short bin (rows 
 constexpr int kSeg = 2048;              // merged positions per wave of the wave and hub bins
 constexpr unsigned int kNone = 0xffffffffu;   // no column: above every column index (columns < ncols <= INT32_MAX)
 
-__device__ inline void ewm_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ inline Index ewm_lower_bound(const Index* __restrict__ a, Index lo, Index hi, Index key) {
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
+// a row's merged length; the intersection drops rows with an empty side
+struct EwmRowLen {
+  const Index* a_ptr;
+  const Index* b_ptr;
+  int intersect;
+  __device__ long long operator()(long long i) const {
+    const Index la = a_ptr[i + 1] - a_ptr[i], lb = b_ptr[i + 1] - b_ptr[i];
+    return intersect && (la == 0 || lb == 0) ? 0 : (long long)(la + lb);
   }
-  return lo;
-}
-
-// rows -> bin lists.  A workgroup bins kBinTile consecutive rows into LDS lists (wave-aggregated LDS appends) and
-// appends each list with one global atomic: one per bin per 2048 rows, not per wave (same-address atomics serialise).
-// A hub row takes ceil(len / kSeg) consecutive segment slots (few rows: one atomic each).
-constexpr int kBinTile = kBlock * 8;
-__global__ __launch_bounds__(kBlock) void ewm_bin_kernel(const Index* __restrict__ a_ptr, const Index* __restrict__ b_ptr, Index m,
-                                                         int intersect, Index* __restrict__ l_short, Index* __restrict__ l_wave,
-                                                         Index* __restrict__ seg_row, Index* __restrict__ seg_k,
-                                                         unsigned int* __restrict__ ctr) {
-  __shared__ Index s_list[2][kBinTile];
-  __shared__ unsigned int s_cnt[2], s_base[2];
-  const int lane = lane_id();
-  for (long long tile = (long long)blockIdx.x * kBinTile; tile < m; tile += (long long)gridDim.x * kBinTile) {
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (int x = threadIdx.x - lane; x < kBinTile; x += kBlock) {   // wave-uniform: x is the wave's first row of the step
-      const long long i = tile + x + lane;
-      int bin = -1;
-      Index len = 0;
-      if (i < m) {
-        const Index la = a_ptr[i + 1] - a_ptr[i], lb = b_ptr[i + 1] - b_ptr[i];
-        len = la + lb;
-        if (len > 0 && !(intersect && (la == 0 || lb == 0))) bin = len <= 2 * kShort ? 0 : len <= kSeg ? 1 : 2;
-      }
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const unsigned long long mask = __ballot(bin == b);
-        if (!mask) continue;
-        const int leader = __ffsll((long long)mask) - 1;
-        unsigned int at = 0;
-        if (lane == leader) at = atomicAdd(&s_cnt[b], (unsigned int)__popcll(mask));
-        at = (unsigned int)__shfl((int)at, leader, kWave);
-        if (bin == b) s_list[b][at + __popcll(mask & ((1ull << lane) - 1ull))] = (Index)i;
-      }
-      if (bin == 2) {
-        const Index nseg = (len + kSeg - 1) / kSeg;
-        const unsigned int at = atomicAdd(&ctr[2], (unsigned int)nseg);
-        for (Index k = 0; k < nseg; ++k) { seg_row[at + k] = (Index)i; seg_k[at + k] = k; }
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) s_base[threadIdx.x] = s_cnt[threadIdx.x] ? atomicAdd(&ctr[threadIdx.x], s_cnt[threadIdx.x]) : 0u;
-    __syncthreads();
-    for (int b = 0; b < 2; ++b) {
-      Index* out = (b == 0 ? l_short : l_wave) + s_base[b];
-      for (unsigned int j = threadIdx.x; j < s_cnt[b]; j += kBlock) out[j] = s_list[b][j];
-    }
-    __syncthreads();
-  }
-}
+};
 
 // One kernel for every bin: groups of G lanes (G = kShort or kWave), each taking one item at a time -- a whole row
 // (seg_k == nullptr) or one kSeg-long segment of a hub row.  kNum = false: counts only.  kAdd: union, else intersection.
@@ -158,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void ewm_merge_kernel(const Index* __restri
       }
       s_a[g0 + t] = av;
       s_b[g0 + t] = bv;
-      ewm_wave_sync();
+      wave_lds_sync();
       int rb = 0, ra = 0;                              // # B window < av, # A window <= bv
 #pragma unroll
       for (int s = G / 2; s > 0; s >>= 1) {
@@ -175,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void ewm_merge_kernel(const Index* __restri
       if constexpr (kNum) partner = __shfl(bval, (lane & ~(G - 1)) + (rb & (G - 1)), kWave);
       const int n_a = __popcll(__ballot(in_a) & gmask);
       const unsigned int last_a = n_a > 0 ? s_a[g0 + n_a - 1] : prev_a;
-      ewm_wave_sync();
+      wave_lds_sync();
       if (in_a) {
         const bool keep = kAdd || pair_a;
         s_col[g0 + t + rb] = keep ? av : kNone;
@@ -185,11 +134,11 @@ __global__ __launch_bounds__(kBlock) void ewm_merge_kernel(const Index* __restri
         s_col[g0 + t + ra] = (kAdd && !dup_b) ? bv : kNone;
         if constexpr (kNum) s_val[g0 + t + ra] = bval;
       }
-      ewm_wave_sync();
+      wave_lds_sync();
       const unsigned int col = t < lim ? s_col[g0 + t] : kNone;
       bool keep = col != kNone;
       if (m_ptr && keep) {
-        const Index p = ewm_lower_bound(m_ind, ms, me, (Index)col);
+        const Index p = index_lower_bound(m_ind, ms, me, (Index)col);
         const bool present = p < me && (unsigned int)m_ind[p] == col && mask_nonzero(m_val, mask_f32, p);
         keep = present != (scmp != 0);
       }
@@ -207,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void ewm_merge_kernel(const Index* __restri
       j0 += lim - n_a;
       prev_a = last_a;
       d += lim;
-      ewm_wave_sync();
+      wave_lds_sync();
     }
     if constexpr (!kNum) {
       if (t == 0) {
@@ -219,16 +168,6 @@ __global__ __launch_bounds__(kBlock) void ewm_merge_kernel(const Index* __restri
       }
     }
   }
-}
-
-// the row counts' total in 64 bits (the u32 scan wraps above 2^32)
-__global__ __launch_bounds__(kBlock) void ewm_count_total_kernel(const unsigned int* __restrict__ counts, Index m,
-                                                                 unsigned long long* __restrict__ total) {
-  unsigned long long acc = 0;
-  const long long stride = (long long)gridDim.x * kBlock;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < m; i += stride) acc += counts[i];
-  acc = wave_sum_u64(acc);
-  if (lane_id() == 0 && acc) atomicAdd(total, acc);
 }
 
 // ---- transposition of a CSR without its CSC
@@ -284,115 +223,43 @@ grb_info ewm_alloc(EwmBuf* b, size_t bytes) {
 }
 
 namespace {
-// the call's one work allocation, carved for the larger of the two orientations
-struct MergeWork {
-  unsigned int* ctr;                                     // [3] bin sizes, then the 64-bit total (8-byte aligned)
-  unsigned long long* total;
-  Index *l_short, *l_wave, *seg_row, *seg_k;
-  unsigned int *seg_cnt, *scan;
-};
+// no length pass: the call's one work allocation has the lists at their upper bounds (every row, and the segments below),
+// carved for the larger of the two orientations
 size_t merge_max_segs(long long nvals_a, long long nvals_b) { return (size_t)(2 * (nvals_a + nvals_b) / kSeg + 2); }
-size_t merge_work_bytes(Index m, size_t max_segs) {
-  const size_t scan = device_scan_u32_scratch((long long)(m > (Index)max_segs ? m : (Index)max_segs) + 1);
-  return 64 + 4 * (2 * (size_t)m + 3 * max_segs + 1) + scan;
-}
-MergeWork carve(void* p, Index m, size_t max_segs) {
-  MergeWork w;
-  w.ctr = (unsigned int*)p;
-  w.total = (unsigned long long*)(w.ctr + 4);
-  w.l_short = (Index*)((char*)p + 64);
-  w.l_wave = w.l_short + m;
-  w.seg_row = w.l_wave + m;
-  w.seg_k = w.seg_row + max_segs;
-  w.seg_cnt = (unsigned int*)(w.seg_k + max_segs);
-  w.scan = w.seg_cnt + max_segs + 1;
-  return w;
-}
-
-inline int capped_grid(long long items, int per_block) {
-  const long long b = (items + per_block - 1) / per_block;
-  return b > 16384 ? 16384 : (int)(b < 1 ? 1 : b);
-}
 
 // one orientation: m rows of op(A) and op(B) (Aa, Bb), the mask's rows (Mm, nullable) -> out
 template <bool kAdd>
 grb_info merge_side(int op, int dtype, Index m, const CsrArrays& Aa, const CsrArrays& Bb, const CsrArrays* Mm, int mask_f32,
-                    int scmp, const MergeWork& w, Side* out) {
+                    int scmp, RowBins& w, Side* out) {
   hipStream_t s = ctx().stream;
   GRB_TRY(ewm_alloc(&out->ptr, 4 * ((size_t)m + 1)));
   unsigned int* counts = (unsigned int*)out->ptr.p;
   GRB_HIP_TRY(hipMemsetAsync(counts, 0, 4 * ((size_t)m + 1), s));
-  GRB_HIP_TRY(hipMemsetAsync(w.ctr, 0, 64, s));
-  if (m > 0) {
-    hipLaunchKernelGGL(ewm_bin_kernel, dim3(stream_grid(m, kBinTile)), dim3(kBlock), 0, s, Aa.ptr, Bb.ptr, m, kAdd ? 0 : 1, w.l_short,
-                       w.l_wave, w.seg_row, w.seg_k, w.ctr);
-    GRB_HIP_TRY(hipGetLastError());
-  }
-  unsigned int nbin[3] = {0, 0, 0};
-  GRB_HIP_TRY(hipMemcpyAsync(nbin, w.ctr, 12, hipMemcpyDeviceToHost, s));
+  GRB_TRY(row_bins_zero_head(&w, s));
+  if (m > 0) GRB_TRY((row_bins_fill<2 * kShort, kSeg>(w, EwmRowLen{Aa.ptr, Bb.ptr, kAdd ? 0 : 1}, m, s)));
+  GRB_HIP_TRY(hipMemcpyAsync(w.nbin, w.d_ctr, 12, hipMemcpyDeviceToHost, s));
   GRB_HIP_TRY(hipStreamSynchronize(s));
-  const int grid_short = capped_grid(nbin[0], kBlock / kShort);
-  const int grid_wave = capped_grid(nbin[1], kWavesPerBlock);
-  const int grid_hub = capped_grid(nbin[2], kWavesPerBlock);
   const Index* mp = Mm ? Mm->ptr : nullptr;
   const Index* mi = Mm ? Mm->ind : nullptr;
   const void* mv = Mm ? Mm->val : nullptr;
   // ---- symbolic (value-free: one instantiation serves every semiring and type)
-  typedef float F;
-  const F* af = (const F*)Aa.val;
-  const F* bf = (const F*)Bb.val;
-  if (nbin[0])
-    hipLaunchKernelGGL((ewm_merge_kernel<GRB_PLUS_MULTIPLIES, F, kShort, false, kAdd>), dim3(grid_short), dim3(kBlock), 0, s, w.l_short,
-                       nullptr, (Index)nbin[0], Aa.ptr, Aa.ind, af, Bb.ptr, Bb.ind, bf, mp, mi, mv, mask_f32, scmp, counts, nullptr,
-                       nullptr, nullptr, nullptr, nullptr);
-  if (nbin[1])
-    hipLaunchKernelGGL((ewm_merge_kernel<GRB_PLUS_MULTIPLIES, F, kWave, false, kAdd>), dim3(grid_wave), dim3(kBlock), 0, s, w.l_wave,
-                       nullptr, (Index)nbin[1], Aa.ptr, Aa.ind, af, Bb.ptr, Bb.ind, bf, mp, mi, mv, mask_f32, scmp, counts, nullptr,
-                       nullptr, nullptr, nullptr, nullptr);
-  if (nbin[2])
-    hipLaunchKernelGGL((ewm_merge_kernel<GRB_PLUS_MULTIPLIES, F, kWave, false, kAdd>), dim3(grid_hub), dim3(kBlock), 0, s, w.seg_row,
-                       w.seg_k, (Index)nbin[2], Aa.ptr, Aa.ind, af, Bb.ptr, Bb.ind, bf, mp, mi, mv, mask_f32, scmp, counts,
-                       w.seg_cnt, nullptr, nullptr, nullptr, nullptr);
-  GRB_HIP_TRY(hipGetLastError());
-  unsigned long long total = 0;
-  if (m > 0) {
-    hipLaunchKernelGGL(ewm_count_total_kernel, dim3(stream_grid(m, kBlock * 8)), dim3(kBlock), 0, s, counts, m, w.total);
-    GRB_HIP_TRY(hipGetLastError());
-    GRB_HIP_TRY(hipMemcpyAsync(&total, w.total, 8, hipMemcpyDeviceToHost, s));
-    GRB_HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (total > (unsigned long long)INT32_MAX) return GRB_OUT_OF_MEMORY;   // grb_index is 32 bits; C keeps what it held
-  out->nnz = (Index)total;
-  GRB_TRY(device_exclusive_scan_u32_in(counts, (long long)m + 1, w.scan));   // counts -> row pointers
-  if (nbin[2]) GRB_TRY(device_exclusive_scan_u32_in(w.seg_cnt, (long long)nbin[2] + 1, w.scan));   // hub segments' offsets
-  out->h_ptr.resize((size_t)m + 1);
-  GRB_HIP_TRY(hipMemcpy(out->h_ptr.data(), counts, 4 * ((size_t)m + 1), hipMemcpyDeviceToHost));
-  GRB_TRY(ewm_alloc(&out->ind, 4 * (size_t)(out->nnz > 0 ? out->nnz : 1)));
-  GRB_TRY(ewm_alloc(&out->val, 4 * (size_t)(out->nnz > 0 ? out->nnz : 1)));
+  GRB_TRY(for_each_bin<kShort>(w, [&](auto g, int grid, const Index* items, const Index* seg_k, Index n) {
+    hipLaunchKernelGGL((ewm_merge_kernel<GRB_PLUS_MULTIPLIES, float, decltype(g)::value, false, kAdd>), dim3(grid), dim3(kBlock), 0, s, items,
+                       seg_k, n, Aa.ptr, Aa.ind, (const float*)Aa.val, Bb.ptr, Bb.ind, (const float*)Bb.val, mp, mi, mv, mask_f32, scmp,
+                       counts, seg_k ? w.seg_cnt : nullptr, nullptr, nullptr, nullptr, nullptr);
+  }));
+  GRB_TRY(row_bins_total(w, counts, m, false, s, out));  // (the merge kernel has added the hub segments into their rows)
+  GRB_TRY(row_bins_pointers(w, m, out));
   if (out->nnz == 0) return GRB_SUCCESS;
   // ---- numeric
   return dispatch_semiring(op, dtype, [&](auto tag, auto tv) -> grb_info {
     using T = decltype(tv);
     constexpr int SR = decltype(tag)::value;
-    const T* av = (const T*)Aa.val;
-    const T* bv = (const T*)Bb.val;
-    const Index* cp = (const Index*)counts;
-    Index* ci = (Index*)out->ind.p;
-    T* cv = (T*)out->val.p;
-    if (nbin[0])
-      hipLaunchKernelGGL((ewm_merge_kernel<SR, T, kShort, true, kAdd>), dim3(grid_short), dim3(kBlock), 0, s, w.l_short, nullptr,
-                         (Index)nbin[0], Aa.ptr, Aa.ind, av, Bb.ptr, Bb.ind, bv, mp, mi, mv, mask_f32, scmp, nullptr, nullptr, cp,
-                         nullptr, ci, cv);
-    if (nbin[1])
-      hipLaunchKernelGGL((ewm_merge_kernel<SR, T, kWave, true, kAdd>), dim3(grid_wave), dim3(kBlock), 0, s, w.l_wave, nullptr,
-                         (Index)nbin[1], Aa.ptr, Aa.ind, av, Bb.ptr, Bb.ind, bv, mp, mi, mv, mask_f32, scmp, nullptr, nullptr, cp,
-                         nullptr, ci, cv);
-    if (nbin[2])
-      hipLaunchKernelGGL((ewm_merge_kernel<SR, T, kWave, true, kAdd>), dim3(grid_hub), dim3(kBlock), 0, s, w.seg_row, w.seg_k,
-                         (Index)nbin[2], Aa.ptr, Aa.ind, av, Bb.ptr, Bb.ind, bv, mp, mi, mv, mask_f32, scmp, nullptr, nullptr, cp,
-                         w.seg_cnt, ci, cv);
-    GRB_HIP_TRY(hipGetLastError());
-    return GRB_SUCCESS;
+    return for_each_bin<kShort>(w, [&](auto g, int grid, const Index* items, const Index* seg_k, Index n) {
+      hipLaunchKernelGGL((ewm_merge_kernel<SR, T, decltype(g)::value, true, kAdd>), dim3(grid), dim3(kBlock), 0, s, items, seg_k, n, Aa.ptr,
+                         Aa.ind, (const T*)Aa.val, Bb.ptr, Bb.ind, (const T*)Bb.val, mp, mi, mv, mask_f32, scmp, nullptr, nullptr,
+                         (const Index*)counts, seg_k ? w.seg_cnt : nullptr, (Index*)out->ind.p, (T*)out->val.p);
+    });
   });
 }
 
@@ -455,9 +322,9 @@ grb_info ewise_matrix(grb_matrix C, grb_matrix mask, int op, grb_matrix A, grb_m
   const CsrArrays& Bc = tran_b ? B->csr : B->csc;
   const int mask_f32 = mask ? (mask->dtype == GRB_F32 ? 1 : 0) : 0;
   const size_t segs = merge_max_segs(A->nvals, B->nvals);
-  EwmBuf work;
-  GRB_TRY(ewm_alloc(&work, merge_work_bytes(both && n > m ? n : m, segs)));
-  const MergeWork w = carve(work.p, both && n > m ? n : m, segs);
+  const size_t rows = (size_t)(both && n > m ? n : m);
+  RowBins w;
+  GRB_TRY(row_bins_carve(&w, rows, rows, segs, (rows > segs ? rows : segs) + 1));
   Side r, c;
   auto run = [&](Index rows, const CsrArrays& X, const CsrArrays& Y, const CsrArrays* M, Side* out) {
     return add ? merge_side<true>(op, A->dtype, rows, X, Y, M, mask_f32, scmp ? 1 : 0, w, out)
@@ -503,9 +370,7 @@ grb_info sort_side(const CsrArrays& X, Index m, Index n, Side* out) {
   if (nv > 0) {
     hipLaunchKernelGGL(ewm_tr_keys_kernel, dim3(stream_grid(nv, kBlock)), dim3(kBlock), 0, s, X.ptr, X.ind, m, nv, keys, pay);
     GRB_HIP_TRY(hipGetLastError());
-    int bits = 1;
-    while (bits < 31 && ((long long)1 << bits) < (long long)n) ++bits;
-    GRB_TRY(device_sort_pairs_range(keys, pay, nv, 0, bits));
+    GRB_TRY(device_sort_pairs_range(keys, pay, nv, 0, index_bits(n)));
     hipLaunchKernelGGL(ewm_tr_gather_kernel, dim3(stream_grid(nv, kBlock)), dim3(kBlock), 0, s, keys, pay,
                        (const unsigned int*)X.val, nv, (Index*)out->ind.p, (unsigned int*)out->val.p);
     GRB_HIP_TRY(hipGetLastError());

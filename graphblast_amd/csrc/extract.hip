@@ -9,7 +9,7 @@
 //             list is validated) needs nothing more: those places ARE the output columns, and a row's output comes out
 //             ascending.  Any other J also gets jpos[] (the places filled in through per-column cursors, in no fixed
 //             order) and the result is ordered afterwards.  A null J is the identity: nothing is built.
-//   bins      output rows by the length of their source row:
+//   bins      output rows by the length of their source row (the shared pipeline of row_bins.hpp):
 //               short  len <= kXShort   a 16-lane group per row, one step (four rows per wave)
 //               wave   len <= kXSeg     a wave per row
 //               hub    the rest         the row cut into segments of kXSeg source entries, a wave each
@@ -27,7 +27,7 @@
 //
 // Column w = X(I, j) and subvector w = u(I): one ascending (index, value) list -- row j of the orientation, or the sparse
 // u -- is probed by binary search for every I[k]; the hits are flagged, scanned and written in order.  A dense u is a gather.
-#include "common.hpp"
+#include "row_bins.hpp"
 
 namespace grb {
 
@@ -35,11 +35,15 @@ constexpr int kXShort = 16;             // the longest source row of the short b
 constexpr int kXSeg = 1024;             // the longest source row of the wave bin; source entries per segment of a hub row
 constexpr unsigned int kXSat = 0x80000000u;   // a count that large is stored as this: the total then fails the INT32_MAX check
 
-__device__ inline int xt_bin_of(Index len) { return len <= 0 ? -1 : len <= kXShort ? 0 : len <= kXSeg ? 1 : 2; }
-__device__ inline Index xt_row_len(const Index* __restrict__ sel, const Index* __restrict__ x_ptr, long long i) {
-  const Index r = sel ? sel[i] : (Index)i;
-  return x_ptr[r + 1] - x_ptr[r];
-}
+// an output row's length for the bins: that of its source row
+struct XtRowLen {
+  const Index* sel;                     // nullptr: output row i is source row i
+  const Index* x_ptr;
+  __device__ long long operator()(long long i) const {
+    const Index r = sel ? sel[i] : (Index)i;
+    return x_ptr[r + 1] - x_ptr[r];
+  }
+};
 
 // inclusive prefix sum inside every 16-lane row of the wave (the first five steps of wave_incl_scan_u32)
 __device__ __forceinline__ unsigned row_incl_scan_u32(unsigned v) {
@@ -65,79 +69,17 @@ __global__ __launch_bounds__(kBlock) void xt_fill_kernel(const Index* __restrict
   }
 }
 
-// ---- sizes of the bins, segments of the hub rows, source entries selected: tot[0 .. 3]
-__global__ __launch_bounds__(kBlock) void xt_len_kernel(const Index* __restrict__ sel, const Index* __restrict__ x_ptr, Index ni,
-                                                        unsigned long long* __restrict__ tot) {
-  unsigned int n_short = 0, n_wave = 0;
-  unsigned long long n_seg = 0, n_len = 0;
+// ---- sizes of the bins, segments of the hub rows, source entries selected: tot[0 .. 3] (row_bins.hpp); row_bin_kernel
+// then fills lists that hold exactly what was counted here
+__global__ __launch_bounds__(kBlock) void xt_len_kernel(XtRowLen len_of, Index ni, unsigned long long* __restrict__ tot) {
+  RowLenSums sums;
   const long long stride = (long long)gridDim.x * kBlock;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < ni; i += stride) {
-    const Index len = xt_row_len(sel, x_ptr, i);
-    const int bin = xt_bin_of(len);
-    n_short += bin == 0;
-    n_wave += bin == 1;
-    if (bin == 2) n_seg += (unsigned long long)((len + kXSeg - 1) / kXSeg);
-    n_len += (unsigned long long)len;
+    const long long len = len_of(i);
+    row_len_add<kXShort, kXSeg>(sums, len);
+    sums.n_own += (unsigned long long)len;
   }
-  n_short = wave_sum_u32(n_short);
-  n_wave = wave_sum_u32(n_wave);
-  n_seg = wave_sum_u64(n_seg);
-  n_len = wave_sum_u64(n_len);
-  if (lane_id() == 0) {
-    if (n_short) atomicAdd(&tot[0], (unsigned long long)n_short);
-    if (n_wave) atomicAdd(&tot[1], (unsigned long long)n_wave);
-    if (n_seg) atomicAdd(&tot[2], n_seg);
-    if (n_len) atomicAdd(&tot[3], n_len);
-  }
-}
-
-// output rows -> bin lists, as ewm_bin_kernel: a workgroup bins kXBinTile consecutive output rows into LDS lists and
-// appends each with one global atomic; a hub row takes ceil(len / kXSeg) consecutive segment slots.  The lists hold
-// exactly what xt_len_kernel counted.
-constexpr int kXBinTile = kBlock * 8;
-__global__ __launch_bounds__(kBlock) void xt_bin_kernel(const Index* __restrict__ sel, const Index* __restrict__ x_ptr, Index ni,
-                                                        Index* __restrict__ l_short, Index* __restrict__ l_wave,
-                                                        Index* __restrict__ seg_row, Index* __restrict__ seg_k,
-                                                        unsigned int* __restrict__ ctr) {
-  __shared__ Index s_list[2][kXBinTile];
-  __shared__ unsigned int s_cnt[2], s_base[2];
-  const int lane = lane_id();
-  for (long long tile = (long long)blockIdx.x * kXBinTile; tile < ni; tile += (long long)gridDim.x * kXBinTile) {
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (int x = threadIdx.x - lane; x < kXBinTile; x += kBlock) {   // wave-uniform: x is the wave's first row of the step
-      const long long i = tile + x + lane;
-      int bin = -1;
-      Index len = 0;
-      if (i < ni) {
-        len = xt_row_len(sel, x_ptr, i);
-        bin = xt_bin_of(len);
-      }
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const unsigned long long mask = __ballot(bin == b);
-        if (!mask) continue;
-        const int leader = __ffsll((long long)mask) - 1;
-        unsigned int at = 0;
-        if (lane == leader) at = atomicAdd(&s_cnt[b], (unsigned int)__popcll(mask));
-        at = (unsigned int)__shfl((int)at, leader, kWave);
-        if (bin == b) s_list[b][at + __popcll(mask & ((1ull << lane) - 1ull))] = (Index)i;
-      }
-      if (bin == 2) {
-        const Index nseg = (len + kXSeg - 1) / kXSeg;
-        const unsigned int at = atomicAdd(&ctr[2], (unsigned int)nseg);
-        for (Index k = 0; k < nseg; ++k) { seg_row[at + k] = (Index)i; seg_k[at + k] = k; }
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) s_base[threadIdx.x] = s_cnt[threadIdx.x] ? atomicAdd(&ctr[threadIdx.x], s_cnt[threadIdx.x]) : 0u;
-    __syncthreads();
-    for (int b = 0; b < 2; ++b) {
-      Index* out = (b == 0 ? l_short : l_wave) + s_base[b];
-      for (unsigned int j = threadIdx.x; j < s_cnt[b]; j += kBlock) out[j] = s_list[b][j];
-    }
-    __syncthreads();
-  }
+  row_len_totals(sums, tot);
 }
 
 // One kernel for every bin and pass: groups of G lanes (kXShort or kWave), an item each -- an output row (seg_k ==
@@ -227,19 +169,6 @@ __global__ __launch_bounds__(kBlock) void xt_rows_kernel(const Index* __restrict
   }
 }
 
-// the 64-bit total of the rows' and the segments' counts (a hub row's own count is still zero here)
-__global__ __launch_bounds__(kBlock) void xt_total_kernel(const unsigned int* __restrict__ counts, Index ni,
-                                                          const unsigned int* __restrict__ seg_cnt, Index nseg,
-                                                          unsigned long long* __restrict__ total) {
-  unsigned long long acc = 0;
-  const long long stride = (long long)gridDim.x * kBlock;
-  const long long first = (long long)blockIdx.x * kBlock + threadIdx.x;
-  for (long long i = first; i < ni; i += stride) acc += counts[i];
-  for (long long i = first; i < nseg; i += stride) acc += seg_cnt[i];
-  acc = wave_sum_u64(acc);
-  if (lane_id() == 0 && acc) atomicAdd(total, acc);
-}
-
 // a hub row's count: the sum of its segments' (consecutive in the list, in order); one thread per first segment
 __global__ __launch_bounds__(kBlock) void xt_fold_kernel(const Index* __restrict__ seg_row, const Index* __restrict__ seg_k, Index nseg,
                                                          const unsigned int* __restrict__ seg_cnt, unsigned int* __restrict__ counts) {
@@ -297,20 +226,6 @@ __global__ __launch_bounds__(kBlock) void xt_gather_kernel(const Index* __restri
   for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride) w[k] = u[sel[k]];
 }
 
-namespace {
-
-inline int xt_grid(long long items, int per_block) {
-  const long long b = (items + per_block - 1) / per_block;
-  return b > 16384 ? 16384 : (int)(b < 1 ? 1 : b);
-}
-inline int xt_bits(Index dim) {
-  int b = 1;
-  while (b < 31 && ((long long)1 << b) < (long long)dim) ++b;
-  return b;
-}
-
-}  // namespace
-
 // (IndexList: common.hpp -- assign_matrix.hip validates and inverts its lists the same way)
 grb_info list_check(IndexList* L, const Index* host, Index n, Index dim) {
   L->host = host;
@@ -361,22 +276,14 @@ grb_info list_invert(IndexList* L) {
 namespace {
 
 template <int kMode>
-grb_info launch_rows(hipStream_t s, const unsigned int* nbin, const Index* l_short, const Index* l_wave, const Index* seg_row,
-                     const Index* seg_k, const Index* sel, const CsrArrays& X, const Index* jptr, const Index* jpos,
-                     unsigned int* counts, unsigned int* seg_cnt, const Index* c_ptr, Index* c_ind, unsigned int* c_val,
-                     unsigned long long* keys, unsigned int* pay) {
-  const unsigned int* xv = (const unsigned int*)X.val;
-  if (nbin[0])
-    hipLaunchKernelGGL((xt_rows_kernel<kXShort, kMode>), dim3(xt_grid(nbin[0], kBlock / kXShort)), dim3(kBlock), 0, s, l_short, nullptr,
-                       (Index)nbin[0], sel, X.ptr, X.ind, xv, jptr, jpos, counts, nullptr, c_ptr, nullptr, c_ind, c_val, keys, pay);
-  if (nbin[1])
-    hipLaunchKernelGGL((xt_rows_kernel<kWave, kMode>), dim3(xt_grid(nbin[1], kWavesPerBlock)), dim3(kBlock), 0, s, l_wave, nullptr,
-                       (Index)nbin[1], sel, X.ptr, X.ind, xv, jptr, jpos, counts, nullptr, c_ptr, nullptr, c_ind, c_val, keys, pay);
-  if (nbin[2])
-    hipLaunchKernelGGL((xt_rows_kernel<kWave, kMode>), dim3(xt_grid(nbin[2], kWavesPerBlock)), dim3(kBlock), 0, s, seg_row, seg_k,
-                       (Index)nbin[2], sel, X.ptr, X.ind, xv, jptr, jpos, counts, seg_cnt, c_ptr, seg_cnt, c_ind, c_val, keys, pay);
-  GRB_HIP_TRY(hipGetLastError());
-  return GRB_SUCCESS;
+grb_info launch_rows(hipStream_t s, const RowBins& b, const Index* sel, const CsrArrays& X, const Index* jptr, const Index* jpos,
+                     unsigned int* counts, const Index* c_ptr, Index* c_ind, unsigned int* c_val, unsigned long long* keys,
+                     unsigned int* pay) {
+  return for_each_bin<kXShort>(b, [&](auto g, int grid, const Index* items, const Index* seg_k, Index n) {
+    unsigned int* seg_cnt = seg_k ? b.seg_cnt : nullptr;   // a segment's count (kMode 0), then its offset
+    hipLaunchKernelGGL((xt_rows_kernel<decltype(g)::value, kMode>), dim3(grid), dim3(kBlock), 0, s, items, seg_k, n, sel, X.ptr, X.ind,
+                       (const unsigned int*)X.val, jptr, jpos, counts, seg_cnt, c_ptr, seg_cnt, c_ind, c_val, keys, pay);
+  });
 }
 
 // one orientation: out = X(R, Cl), X's rows selected by R, its columns by Cl
@@ -386,87 +293,50 @@ grb_info extract_side(const CsrArrays& X, IndexList* R, IndexList* Cl, Side* out
   GRB_TRY(list_upload(R));
   GRB_TRY(list_invert(Cl));
   const Index* sel = R->dev();
+  const XtRowLen len_of{sel, X.ptr};
   GRB_TRY(ewm_alloc(&out->ptr, 4 * ((size_t)ni + 1)));
   unsigned int* counts = (unsigned int*)out->ptr.p;
   GRB_HIP_TRY(hipMemsetAsync(counts, 0, 4 * ((size_t)ni + 1), s));
-  EwmBuf head;                                           // [4] 64-bit sizes, [3] list cursors, the 64-bit total
-  GRB_TRY(ewm_alloc(&head, 64));
-  GRB_HIP_TRY(hipMemsetAsync(head.p, 0, 64, s));
-  unsigned long long* d_tot = (unsigned long long*)head.p;
-  unsigned int* d_ctr = (unsigned int*)(d_tot + 4);
-  unsigned long long* d_total = d_tot + 6;
-  unsigned long long tot[4] = {0, 0, 0, 0};
+  // an output row appears once per occurrence in I, so nothing bounds the bins beforehand: a length pass sizes them
+  RowBins b;
+  GRB_TRY(row_bins_head(&b, s));
   if (ni > 0) {
-    hipLaunchKernelGGL(xt_len_kernel, dim3(stream_grid(ni, kBlock * 8)), dim3(kBlock), 0, s, sel, X.ptr, ni, d_tot);
+    hipLaunchKernelGGL(xt_len_kernel, dim3(stream_grid(ni, kBlock * 8)), dim3(kBlock), 0, s, len_of, ni, b.d_tot);
     GRB_HIP_TRY(hipGetLastError());
-    GRB_HIP_TRY(hipMemcpyAsync(tot, d_tot, 32, hipMemcpyDeviceToHost, s));
-    GRB_HIP_TRY(hipStreamSynchronize(s));
   }
+  GRB_TRY(row_bins_sized(&b, ni, s));
   // every column selected once (a null list): the result has the selected source entries, known already
-  if (!Cl->host && tot[3] > (unsigned long long)INT32_MAX) return GRB_OUT_OF_MEMORY;
-  if (tot[2] > (unsigned long long)INT32_MAX) return GRB_OUT_OF_MEMORY;   // (more than 2^41 source entries to visit)
-  const unsigned int nbin[3] = {(unsigned int)tot[0], (unsigned int)tot[1], (unsigned int)tot[2]};
-  const size_t nseg = nbin[2];
-  const size_t scan_len = ((size_t)ni > nseg ? (size_t)ni : nseg) + 1;
-  EwmBuf work;
-  GRB_TRY(ewm_alloc(&work, 4 * ((size_t)nbin[0] + nbin[1] + 3 * nseg + 1) + device_scan_u32_scratch((long long)scan_len)));
-  Index* l_short = (Index*)work.p;
-  Index* l_wave = l_short + nbin[0];
-  Index* seg_row = l_wave + nbin[1];
-  Index* seg_k = seg_row + nseg;
-  unsigned int* seg_cnt = (unsigned int*)(seg_k + nseg);
-  unsigned int* scan = seg_cnt + nseg + 1;
-  if (ni > 0) {
-    hipLaunchKernelGGL(xt_bin_kernel, dim3(stream_grid(ni, kXBinTile)), dim3(kBlock), 0, s, sel, X.ptr, ni, l_short, l_wave, seg_row,
-                       seg_k, d_ctr);
-    GRB_HIP_TRY(hipGetLastError());
-  }
-  GRB_HIP_TRY(hipMemsetAsync(seg_cnt, 0, 4 * (nseg + 1), s));
+  if (!Cl->host && b.own > (unsigned long long)INT32_MAX) return GRB_OUT_OF_MEMORY;
+  if (ni > 0) GRB_TRY((row_bins_fill<kXShort, kXSeg>(b, len_of, ni, s)));
   // ---- symbolic
-  GRB_TRY(launch_rows<0>(s, nbin, l_short, l_wave, seg_row, seg_k, sel, X, Cl->jptr(), nullptr, counts, seg_cnt, nullptr, nullptr,
-                         nullptr, nullptr, nullptr));
-  unsigned long long total = 0;
-  if (ni > 0) {
-    hipLaunchKernelGGL(xt_total_kernel, dim3(stream_grid((long long)scan_len, kBlock * 8)), dim3(kBlock), 0, s, counts, ni, seg_cnt,
-                       (Index)nseg, d_total);
-    GRB_HIP_TRY(hipGetLastError());
-    GRB_HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
-    GRB_HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (total > (unsigned long long)INT32_MAX) return GRB_OUT_OF_MEMORY;   // grb_index is 32 bits; C keeps what it held
-  out->nnz = (Index)total;
-  if (nseg) {
-    hipLaunchKernelGGL(xt_fold_kernel, dim3(stream_grid((long long)nseg, kBlock)), dim3(kBlock), 0, s, seg_row, seg_k, (Index)nseg, seg_cnt,
-                       counts);
+  GRB_TRY(launch_rows<0>(s, b, sel, X, Cl->jptr(), nullptr, counts, nullptr, nullptr, nullptr, nullptr, nullptr));
+  GRB_TRY(row_bins_total(b, counts, ni, true, s, out));  // (a hub row's own count is still zero here)
+  if (b.nbin[2]) {
+    hipLaunchKernelGGL(xt_fold_kernel, dim3(stream_grid((long long)b.nbin[2], kBlock)), dim3(kBlock), 0, s, b.seg_row, b.seg_k,
+                       (Index)b.nbin[2], b.seg_cnt, counts);
     GRB_HIP_TRY(hipGetLastError());
   }
-  GRB_TRY(device_exclusive_scan_u32_in(counts, (long long)ni + 1, scan));   // counts -> row pointers
-  if (nseg) GRB_TRY(device_exclusive_scan_u32_in(seg_cnt, (long long)nseg + 1, scan));   // hub segments' offsets
-  out->h_ptr.resize((size_t)ni + 1);
-  GRB_HIP_TRY(hipMemcpy(out->h_ptr.data(), counts, 4 * ((size_t)ni + 1), hipMemcpyDeviceToHost));
-  const size_t cap = (size_t)(out->nnz > 0 ? out->nnz : 1);
+  GRB_TRY(row_bins_pointers(b, ni, out, false));
   // ---- numeric
   if (Cl->sorted) {
-    GRB_TRY(ewm_alloc(&out->ind, 4 * cap));
-    GRB_TRY(ewm_alloc(&out->val, 4 * cap));
+    GRB_TRY(side_alloc_entries(out));
     if (out->nnz == 0) return GRB_SUCCESS;
-    GRB_TRY(launch_rows<1>(s, nbin, l_short, l_wave, seg_row, seg_k, sel, X, Cl->jptr(), nullptr, nullptr, seg_cnt,
-                           (const Index*)counts, (Index*)out->ind.p, (unsigned int*)out->val.p, nullptr, nullptr));
+    GRB_TRY(launch_rows<1>(s, b, sel, X, Cl->jptr(), nullptr, nullptr, (const Index*)counts, (Index*)out->ind.p,
+                           (unsigned int*)out->val.p, nullptr, nullptr));
     GRB_HIP_TRY(hipStreamSynchronize(s));                // (the lists are freed on the way out)
     return GRB_SUCCESS;
   }
   // J in no order: (row, column) keys, sorted over the bits the two dimensions need
+  const size_t cap = (size_t)(out->nnz > 0 ? out->nnz : 1);
   EwmBuf pairs;
   if (out->nnz > 0) {
     GRB_TRY(ewm_alloc(&pairs, 12 * cap));
     unsigned long long* keys = (unsigned long long*)pairs.p;
     unsigned int* pay = (unsigned int*)(keys + cap);
-    GRB_TRY(launch_rows<2>(s, nbin, l_short, l_wave, seg_row, seg_k, sel, X, Cl->jptr(), Cl->jpos(), nullptr, seg_cnt,
-                           (const Index*)counts, nullptr, nullptr, keys, pay));
-    GRB_TRY(device_sort_pairs(keys, pay, out->nnz, xt_bits(Cl->n), xt_bits(ni)));
+    GRB_TRY(launch_rows<2>(s, b, sel, X, Cl->jptr(), Cl->jpos(), nullptr, (const Index*)counts, nullptr, nullptr, keys, pay));
+    GRB_TRY(device_sort_pairs(keys, pay, out->nnz, index_bits(Cl->n), index_bits(ni)));
   }
-  GRB_TRY(ewm_alloc(&out->ind, 4 * cap));
-  GRB_TRY(ewm_alloc(&out->val, 4 * cap));
+  GRB_TRY(side_alloc_entries(out));
   if (out->nnz > 0) {
     hipLaunchKernelGGL(xt_unpack_kernel, dim3(stream_grid(out->nnz, kBlock)), dim3(kBlock), 0, s, (const unsigned long long*)pairs.p,
                        (const unsigned int*)((const unsigned long long*)pairs.p + cap), out->nnz, (Index*)out->ind.p,
@@ -476,6 +346,7 @@ grb_info extract_side(const CsrArrays& X, IndexList* R, IndexList* Cl, Side* out
   }
   return GRB_SUCCESS;
 }
+
 
 // w <- the entries k where sel[k] (k itself for a null list) is in the ascending list (l_ind, l_val); w becomes sparse
 grb_info probe_into(grb_vector w, const IndexList& L, const Index* l_ind, const void* l_val, Index l_n) {

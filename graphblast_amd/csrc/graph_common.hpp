@@ -8,16 +8,7 @@
 
 namespace grb {
 
-// ---- device: searches in a row ---------------------------------------------------------------------------------------------
-// the first position in [lo, hi) whose index is >= x (hi if none): indices ascend
-__device__ __forceinline__ Index index_lower_bound(const Index* __restrict__ a, Index lo, Index hi, Index x) {
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
+// ---- device: searches in a row (index_lower_bound: common.hpp) ------------------------------------------------------------
 // the length of v's row (or column) without a stored diagonal
 __device__ __forceinline__ int row_degree_no_diag(const Index* __restrict__ ptr, const Index* __restrict__ ind, Index v) {
   const Index b = ptr[v], e = ptr[v + 1];

@@ -26,26 +26,13 @@
 //            folded in order: the cost follows the products whatever the columns' spread.
 // The symbolic pass skips the values.  Temporaries: the row pointers (m + 1), four row lists (4 m) and the
 // result arrays; nothing is proportional to the number of products.
-#include "common.hpp"
+#include "row_bins.hpp"
 
 namespace grb {
 
 constexpr int kTinySmall = 16;         // lanes per row of the first bin
 constexpr int kWideCols = 4096;        // columns per window of the wide kernel (16 KiB of values + 512 B of bits per wave)
 constexpr int kMidCap = 1024;          // products per row of the mid bin (8 KiB of keys + 4 KiB of values per wave)
-
-__device__ inline void spgemm_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ inline Index spgemm_lower_bound(const Index* __restrict__ a, Index lo, Index hi, Index key) {
-  while (lo < hi) {
-    const Index mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // ascending bitonic sort of (key, val) across aligned groups of L lanes; keys are distinct but for the sentinel
 template <int L, typename K, typename V>
@@ -160,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void spgemm_tiny_kernel(const Index* __rest
     } else {
       s_key[threadIdx.x] = key;
       s_prod[threadIdx.x] = prod;
-      spgemm_wave_sync();
+      wave_lds_sync();
       if (head) {
         const int g0 = threadIdx.x - t;
         T acc = S::identity();
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void spgemm_tiny_kernel(const Index* __rest
         c_ind[pos] = (Index)(key >> 6);
         c_val[pos] = acc;
       }
-      spgemm_wave_sync();
+      wave_lds_sync();
     }
   }
 }
@@ -221,7 +208,7 @@ __global__ __launch_bounds__(kWave) void spgemm_wide_kernel(const Index* __restr
       const Index wlo = (Index)w0;
       const Index whi = (Index)((long long)jend < w0 + kWideCols ? (long long)jend : w0 + kWideCols);
       for (int i = lane; i < kWords; i += kWave) s_bits[i] = 0u;
-      spgemm_wave_sync();
+      wave_lds_sync();
       for (Index c0 = as; c0 < ae; c0 += kWave) {
         const Index e = c0 + lane;
         Index lo = 0, len = 0;
@@ -231,8 +218,8 @@ __global__ __launch_bounds__(kWave) void spgemm_wide_kernel(const Index* __restr
           const Index k = a_ind[e];
           const Index bs = b_ptr[k], be = b_ptr[k + 1];
           if (be > bs) {
-            lo = b_ind[bs] >= wlo ? bs : spgemm_lower_bound(b_ind, bs, be, wlo);
-            const Index hi = b_ind[be - 1] < whi ? be : spgemm_lower_bound(b_ind, lo, be, whi);
+            lo = b_ind[bs] >= wlo ? bs : index_lower_bound(b_ind, bs, be, wlo);
+            const Index hi = b_ind[be - 1] < whi ? be : index_lower_bound(b_ind, lo, be, whi);
             len = hi - lo;                                 // <= kWideCols: a row's columns are distinct
             if (hi < be) nxt = (unsigned int)b_ind[hi];
           }
@@ -245,7 +232,7 @@ __global__ __launch_bounds__(kWave) void spgemm_wide_kernel(const Index* __restr
         s_off[lane] = (Index)incl - len;
         s_lo[lane] = lo;
         if constexpr (kNum) s_a[lane] = a;
-        spgemm_wave_sync();
+        wave_lds_sync();
         for (Index x0 = 0; x0 < total; x0 += kWave) {
           const Index x = x0 + lane;
           const bool valid = x < total;
@@ -269,7 +256,7 @@ __global__ __launch_bounds__(kWave) void spgemm_wide_kernel(const Index* __restr
             spgemm_group_sort<kWave>(key, prod, lane);
             s_key[lane] = key;
             s_prod[lane] = prod;
-            spgemm_wave_sync();
+            wave_lds_sync();
             const unsigned int prev = lane > 0 ? s_key[lane - 1] : 0xffffffffu;
             const bool head = key != 0xffffffffu && (lane == 0 || (prev >> 6) != (key >> 6));
             if (head) {
@@ -280,7 +267,7 @@ __global__ __launch_bounds__(kWave) void spgemm_wide_kernel(const Index* __restr
               atomicOr(&s_bits[jr >> 5], bit);
             }
           }
-          spgemm_wave_sync();
+          wave_lds_sync();
         }
       }
       // the window's columns, ascending
@@ -303,7 +290,7 @@ __global__ __launch_bounds__(kWave) void spgemm_wide_kernel(const Index* __restr
         out += (Index)tot;
         cnt += tot;
       }
-      spgemm_wave_sync();
+      wave_lds_sync();
       w0 = wnext;                                        // (> the window: the loop ends when no partner has more)
     }
     if constexpr (!kNum)
@@ -348,7 +335,7 @@ __global__ __launch_bounds__(kWave) void spgemm_mid_kernel(const Index* __restri
       s_off[lane] = (Index)incl - len;
       s_lo[lane] = lo;
       if constexpr (kNum) s_a[lane] = a;
-      spgemm_wave_sync();
+      wave_lds_sync();
       for (Index x = lane; x < total; x += kWave) {
         int o = 0;
 #pragma unroll
@@ -360,13 +347,13 @@ __global__ __launch_bounds__(kWave) void spgemm_mid_kernel(const Index* __restri
         if constexpr (kNum) s_val[at] = S::mul(s_a[o], b_val[q]);
       }
       np += total;
-      spgemm_wave_sync();
+      wave_lds_sync();
     }
     // ---- sort the np keys (padded to a power of two with the largest key)
     int P = kWave;
     while (P < np) P <<= 1;
     for (int i = np + lane; i < P; i += kWave) s_key[i] = ~0ull;
-    spgemm_wave_sync();
+    wave_lds_sync();
     for (int k = 2; k <= P; k <<= 1) {
       for (int j = k >> 1; j > 0; j >>= 1) {
         for (int i = lane; i < P; i += kWave) {
@@ -380,7 +367,7 @@ __global__ __launch_bounds__(kWave) void spgemm_mid_kernel(const Index* __restri
             }
           }
         }
-        spgemm_wave_sync();
+        wave_lds_sync();
       }
     }
     // ---- runs of one column: count them, fold each in order
@@ -406,36 +393,9 @@ __global__ __launch_bounds__(kWave) void spgemm_mid_kernel(const Index* __restri
     }
     if constexpr (!kNum)
       if (lane == 0) counts[r] = cnt;
-    spgemm_wave_sync();
+    wave_lds_sync();
   }
 }
-
-// the row counts' total in 64 bits (the u32 scan wraps above 2^32)
-__global__ __launch_bounds__(kBlock) void spgemm_count_total_kernel(const unsigned int* __restrict__ counts, Index m,
-                                                                    unsigned long long* __restrict__ total) {
-  unsigned long long acc = 0;
-  const long long stride = (long long)gridDim.x * kBlock;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < m; i += stride) acc += counts[i];
-  acc = wave_sum_u64(acc);
-  if (lane_id() == 0 && acc) atomicAdd(total, acc);
-}
-
-namespace {
-// device memory of one call: freed on the way out unless released to C
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  void* release() { void* q = p; p = nullptr; return q; }
-};
-grb_info spgemm_alloc(DevBuf* b, size_t bytes) {
-  if (hipMalloc(&b->p, bytes ? bytes : 4) != hipSuccess) {
-    (void)hipGetLastError();                             // (the failed allocation leaves its error behind)
-    b->p = nullptr;
-    return GRB_OUT_OF_MEMORY;
-  }
-  return GRB_SUCCESS;
-}
-}  // namespace
 
 grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool tran_a, bool tran_b) {
   if (C == A || C == B) return GRB_NOT_IMPLEMENTED;
@@ -449,10 +409,10 @@ grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool 
   if (Aa.n != m || Bb.n != kb) return GRB_INVALID_OBJECT;   // (a CSR-only matrix's "CSC" of another shape)
   hipStream_t s = ctx().stream;
   // ---- bins
-  DevBuf d_ptr, d_work;
+  EwmBuf d_ptr, d_work;
   const size_t scan_bytes = device_scan_u32_scratch((long long)m + 1);
-  GRB_TRY(spgemm_alloc(&d_ptr, 4 * ((size_t)m + 1)));
-  GRB_TRY(spgemm_alloc(&d_work, 64 + 4 * 4 * (size_t)m + scan_bytes));
+  GRB_TRY(ewm_alloc(&d_ptr, 4 * ((size_t)m + 1)));
+  GRB_TRY(ewm_alloc(&d_work, 64 + 4 * 4 * (size_t)m + scan_bytes));
   unsigned int* counts = (unsigned int*)d_ptr.p;
   unsigned int* ctr = (unsigned int*)d_work.p;            // [4] bin sizes, then the 64-bit total (8-byte aligned)
   unsigned long long* d_total = (unsigned long long*)(ctr + 4);
@@ -471,10 +431,8 @@ grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool 
   const Index* l64 = lists + m;
   const Index* lmid = lists + 2 * (size_t)m;
   const Index* lwide = lists + 3 * (size_t)m;
-  const int tiny16_grid = ceil_div(nbin[0], (long long)kBlock / kTinySmall) > 16384 ? 16384 : ceil_div(nbin[0], kBlock / kTinySmall);
-  const int tiny64_grid = ceil_div(nbin[1], (long long)kWavesPerBlock) > 16384 ? 16384 : ceil_div(nbin[1], kWavesPerBlock);
-  const int mid_grid = nbin[2] > 16384u ? 16384 : (int)nbin[2];
-  const int wide_grid = nbin[3] > 16384u ? 16384 : (int)nbin[3];
+  const int tiny16_grid = capped_grid(nbin[0], kBlock / kTinySmall), tiny64_grid = capped_grid(nbin[1], kWavesPerBlock);
+  const int mid_grid = capped_grid(nbin[2], 1), wide_grid = capped_grid(nbin[3], 1);   // (a wave per row: one-wave workgroups)
   const float* av = (const float*)Aa.val;
   const float* bv = (const float*)Bb.val;
   // ---- symbolic (semiring-free: the plus-times instantiation without values)
@@ -489,7 +447,7 @@ grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool 
   GRB_HIP_TRY(hipGetLastError());
   unsigned long long total = 0;
   if (m > 0) {
-    hipLaunchKernelGGL(spgemm_count_total_kernel, dim3(stream_grid(m, kBlock * 8)), dim3(kBlock), 0, s, counts, m, d_total);
+    hipLaunchKernelGGL(count_total_kernel, dim3(stream_grid(m, kBlock * 8)), dim3(kBlock), 0, s, counts, m, nullptr, 0, d_total);
     GRB_HIP_TRY(hipGetLastError());
     GRB_HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
     GRB_HIP_TRY(hipStreamSynchronize(s));
@@ -499,9 +457,9 @@ grb_info spgemm_unmasked(grb_matrix C, int op, grb_matrix A, grb_matrix B, bool 
   GRB_TRY(device_exclusive_scan_u32_in(counts, (long long)m + 1, scan_totals));   // counts -> row pointers
   std::vector<Index> h_ptr((size_t)m + 1);
   GRB_HIP_TRY(hipMemcpy(h_ptr.data(), counts, 4 * ((size_t)m + 1), hipMemcpyDeviceToHost));
-  DevBuf d_ind, d_val;
-  GRB_TRY(spgemm_alloc(&d_ind, 4 * (size_t)(nnz > 0 ? nnz : 1)));
-  GRB_TRY(spgemm_alloc(&d_val, 4 * (size_t)(nnz > 0 ? nnz : 1)));
+  EwmBuf d_ind, d_val;
+  GRB_TRY(ewm_alloc(&d_ind, 4 * (size_t)(nnz > 0 ? nnz : 1)));
+  GRB_TRY(ewm_alloc(&d_val, 4 * (size_t)(nnz > 0 ? nnz : 1)));
   // ---- numeric
   if (nnz > 0) {
     GRB_TRY(dispatch_semiring(op, GRB_F32, [&](auto tag, auto t) -> grb_info {
