@@ -1113,6 +1113,10 @@ grb_info grb_mxm(grb_matrix C, grb_matrix mask, grb_accum accum, grb_semiring op
   const CsrArrays& Bb = tran_b ? B->csr : B->csc;        // "columns of B"
   if (!Aa.ptr || !Bb.ptr || !mask->csr.ptr) return GRB_INVALID_OBJECT;
   if (Aa.n != mask->nrows || C->nrows != mask->nrows || C->ncols != mask->ncols) return GRB_DIMENSION_MISMATCH;
+  // op(B)'s columns are the mask's (the kernels index B's lists by the mask's column ids), and the two operands share
+  // the dimension they are folded over -- checked before C is touched, as the unmasked product does
+  const Index inner_a = tran_a ? A->nrows : A->ncols, inner_b = tran_b ? B->ncols : B->nrows;
+  if (Bb.n != mask->ncols || inner_a != inner_b) return GRB_DIMENSION_MISMATCH;
   hipStream_t s = ctx().stream;
   // C takes the mask's structure (C->dup(&mask->sparse_), spgemm.hpp:78-79)
   // whatever C held before goes, with the per-graph side arrays that described it (skip bitmaps,

@@ -66,8 +66,12 @@ def test_every_semiring_with_values_and_zero_mask_entries(hb, dt):
 
 @pytest.mark.parametrize("scale,values", [(15, "ones"), (15, "int"), (18, "ones"), (18, "int")])
 def test_long_pivots_on_rmat_sampled_entries(hb, scale, values):
-    """hub rows of thousands (scale 15: the workgroup kernel's LDS tables) and tens of thousands of entries (scale 18:
-    the 128 KiB tables and the global-memory arena); stored values take the key + value slots, ones the key-only ones"""
+    """hub rows of thousands (scale 15) and tens of thousands of entries (scale 18).  Stored values take the (key, value)
+    slots: 64 KiB and 128 KiB LDS tables, the longest pivots in segments.  With ones both sides hold one value: MinimumPlus
+    takes the key-only tables the same way, but PlusMultiplies -- an int32 plus-monoid -- sends every pivot of more than
+    GRB_TC_BITMAP_MIN (2048 by default) entries to the bitmap kernel, over a single range of columns here, so the compact
+    key-only path sees 64 KiB tables only (the longer ones: tests/test_gpu_mxm_masked_routes.py, in a child process
+    under GRB_TC_BITMAP_MIN=0)"""
     import torch
     from oracle.semiring import Semiring
     from graphblast_amd.graphgen import rmat_edges, finalize_edges

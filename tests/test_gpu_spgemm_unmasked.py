@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from backends import HipBackend
+from mxm_masked_cases import fold as _fold        # the ascending-k join, shared with the masked product's tests
 
 pytestmark = pytest.mark.gpu
 
@@ -44,32 +45,6 @@ class _Registered:
 
     def identity(self):
         return self._id
-
-
-def _fold(sr, m, n, ap, ai, av, bp, bi, bv):
-    """C = A (+.x) B in CSR, each entry acc = add(mul(a_ik, b_kj), acc) over k ascending (stored zeros kept)"""
-    rows = np.repeat(np.arange(m), np.diff(ap))
-    lens = np.diff(bp)[ai]
-    tot = int(lens.sum())
-    if tot == 0:
-        return np.zeros(m + 1, np.int32), np.zeros(0, np.int32), np.zeros(0, F)
-    ent = np.repeat(np.arange(ai.size), lens)
-    q = bp[ai[ent]] + (np.arange(tot) - np.repeat(np.cumsum(lens) - lens, lens))
-    pi, pj, pk = rows[ent], bi[q], ai[ent]
-    prod = sr.mul_op(av[ent], bv[q])
-    order = np.lexsort((pk, pj, pi))
-    pi, pj, prod = pi[order], pj[order], prod[order]
-    key = pi.astype(np.int64) * n + pj
-    start = np.r_[True, key[1:] != key[:-1]]
-    gid = np.cumsum(start) - 1
-    rank = np.arange(tot) - np.flatnonzero(start)[gid]
-    acc = np.full(int(gid[-1]) + 1, sr.identity(), dtype=F)
-    for r in range(int(rank.max()) + 1):
-        sel = rank == r
-        acc[gid[sel]] = sr.add_op(prod[sel], acc[gid[sel]])
-    cp = np.zeros(m + 1, np.int32)
-    np.cumsum(np.bincount(pi[start], minlength=m), out=cp[1:])
-    return cp, pj[start].astype(np.int32), acc
 
 
 def _desc(hb, ta, tb):
