@@ -218,6 +218,7 @@ _SIGS = {
     "grb_spmv_plan_info": [_vp, _i, _i, C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_i)],
     "grb_bfs_batch": [_vp, _i, _vp, _vp, _vp, _vp],
     "grb_bfs_batch_set_tail": [C.c_longlong],
+    "grb_bfs_batch_hot": [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _vp, C.c_longlong],
     "grb_descriptor_iter_log": [_vp, _vp, _i, C.POINTER(_i)],
     "grb_cache_name": [C.c_char_p, _i, C.c_char_p, C.c_size_t],
     "grb_matrix_write_cache": [_vp, C.c_char_p],

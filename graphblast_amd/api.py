@@ -674,6 +674,19 @@ def bfs_batch_set_tail(edges=-1):
     return int(_lib.load().grb_bfs_batch_set_tail(int(edges)))
 
 
+def bfs_batch_hot(A):
+    """The hot block the batched traversal keeps for A (grb_bfs_batch_hot; built if A has none yet): dict(H, t, cap, hubs) --
+    the hubs are the vertices of out-degree >= t, ascending; H = 0: A sweeps without one."""
+    lib = _lib.load()
+    H, t, cap = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    info = lib.grb_bfs_batch_hot(_h(A), C.byref(H), C.byref(t), C.byref(cap), None, 0)
+    assert info == 0, info
+    hubs = np.zeros(max(int(H.value), 1), dtype=np.int32)
+    info = lib.grb_bfs_batch_hot(_h(A), None, None, None, hubs.ctypes.data, int(H.value))
+    assert info == 0, info
+    return dict(H=int(H.value), t=int(t.value), cap=int(cap.value), hubs=hubs[:int(H.value)])
+
+
 def sssp(v, A, s, desc):
     res = AlgoResult()
     info = _lib.load().grb_sssp(_h(v), _h(A), int(s), _h(desc), C.byref(res))

@@ -768,8 +768,39 @@ struct DecideArgs {
                                       // knows the level's masks whoever decided them -- it read them from the box
   u64* ctl;
 };
-__global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64* box, u64 seq, DecideArgs d) {
+// ---- the hot block ---------------------------------------------------------------------------------------------------
+// A pulled entry is a random line of the frontier words, and most entries name few vertices: on RMAT-22 the 64 Ki
+// vertices of largest out-degree are 62 % of the CSC entries, each alone on its 128-byte line among fifteen cold words.
+// Their words are kept a second time, side by side behind the n words of every array a pull can read as its frontier
+// (0.5 MiB for 64 Ki hubs: an eighth of an XCD's L2), and the pull kernels gather through copies of the CSC indices and
+// of the hint that name hub j as n + j.  The vertex numbering, the probe order and every result stay what they are.  The
+// tail must be current before a pull reads the array: the copy below runs between the array's last writer and that
+// pull, in stream order.  Measured (docs/experiments.md R26): level 3's pull fetches half the bytes and runs 151 -> 124 us
+// at K = 32; the levels bound by dependent latency do not move.
+struct HotCopy {
+  u64* words;                         // the level's words, n of them, and H more behind them
+  const Index* hubs;
+  Index n, H;                         // H = 0: nothing to copy
+};
+__device__ inline void batch_hot_copy(const HotCopy& h, Index first, Index stride) {
+  for (Index j = first; j < h.H; j += stride) h.words[(size_t)h.n + j] = h.words[h.hubs[j]];
+}
+// ... as a launch of its own, where no totals launch sits between the writer and the pull (the seed kernel before a first
+// level that pulls, a light-level launch that hands a level back)
+__global__ __launch_bounds__(kBlock) void batch_hot_refresh_kernel(HotCopy h) {
+  batch_hot_copy(h, (Index)blockIdx.x * blockDim.x + threadIdx.x, (Index)gridDim.x * blockDim.x);
+}
+constexpr int kHotCopyBlocks = 512;   // at most; 256 words each per round
+static inline int hot_copy_blocks(Index H) { return H > 0 ? std::min<int>(ceil_div(H, kBlock), kHotCopyBlocks) : 0; }
+
+// Workgroup 0 sums and decides; the others (hot_copy_blocks of them) bring the tail of the level's words up to date -- they
+// cannot know what is decided, so they always copy.
+__global__ __launch_bounds__(kBlock) void batch_totals_kernel(u64* counters, u64* box, u64 seq, DecideArgs d, HotCopy hot) {
   __shared__ u64 s_nf[64], s_mf[64], s_open;
+  if (blockIdx.x > 0) {
+    batch_hot_copy(hot, (Index)(blockIdx.x - 1) * blockDim.x + threadIdx.x, (Index)(gridDim.x - 1) * blockDim.x);
+    return;
+  }
   const int i = threadIdx.x;
   if (i < kBatchCounters) {
     u64 t = 0;
@@ -1190,6 +1221,48 @@ __global__ void batch_unlabel_kernel(BatchArgs a, float bad) {
       if (a.label[s][i] == bad) a.label[s][i] = 0.f;
 }
 
+// ---- the hot block's preparation, once per matrix ----------------------------------------------------------------------
+// The threshold is found by selecting the (cap + 1)-th largest out-degree digit by digit: a pass counts, in LDS, one
+// 11-bit digit of the degrees that agree with the digits chosen so far (the host reads 2048 counts, never a degree).
+constexpr int kHotDigitBits = 11, kHotBins = 1 << kHotDigitBits;
+__global__ __launch_bounds__(kBlock) void batch_hot_hist_kernel(const Index* __restrict__ optr, Index n, unsigned int above_mask,
+                                                                unsigned int above_value, int shift, unsigned int* __restrict__ bins) {
+  __shared__ unsigned int s_bins[kHotBins];
+  for (int i = threadIdx.x; i < kHotBins; i += blockDim.x) s_bins[i] = 0u;
+  __syncthreads();
+  for (Index v = (Index)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (Index)gridDim.x * blockDim.x) {
+    const unsigned int d = (unsigned int)(optr[v + 1] - optr[v]);
+    if ((d & above_mask) == above_value) atomicAdd(&s_bins[(d >> shift) & (unsigned int)(kHotBins - 1)], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kHotBins; i += blockDim.x)
+    if (s_bins[i]) atomicAdd(&bins[i], s_bins[i]);
+}
+// flag[v] = 1 for a hub, flag[n] = 0: scanned, flag[v] is the hub's slot and flag[n] is H
+__global__ __launch_bounds__(kBlock) void batch_hot_flag_kernel(const Index* __restrict__ optr, Index n, unsigned int t,
+                                                                unsigned int* __restrict__ flag) {
+  for (Index v = (Index)blockIdx.x * blockDim.x + threadIdx.x; v <= n; v += (Index)gridDim.x * blockDim.x)
+    flag[v] = v < n && (unsigned int)(optr[v + 1] - optr[v]) >= t ? 1u : 0u;
+}
+// the scanned flags become the table old name -> new name, in place; the hubs are listed by slot
+__global__ __launch_bounds__(kBlock) void batch_hot_names_kernel(const Index* __restrict__ optr, Index n, unsigned int t,
+                                                                 unsigned int* __restrict__ slot_then_name, Index* __restrict__ hubs) {
+  for (Index v = (Index)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (Index)gridDim.x * blockDim.x) {
+    const bool hub = (unsigned int)(optr[v + 1] - optr[v]) >= t;
+    const unsigned int j = slot_then_name[v];
+    if (hub) hubs[j] = v;
+    slot_then_name[v] = hub ? (unsigned int)n + j : (unsigned int)v;
+  }
+}
+// out[i] = name[in[i]]; an entry that names no vertex (the hint of a row without entries: -1) stays
+__global__ __launch_bounds__(kBlock) void batch_hot_rename_kernel(const Index* __restrict__ in, long long count, Index n,
+                                                                  const unsigned int* __restrict__ name, Index* __restrict__ out) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x) {
+    const Index c = in[i];
+    out[i] = c >= 0 && c < n ? (Index)name[c] : c;
+  }
+}
+
 }  // namespace grb
 
 using namespace grb;
@@ -1298,6 +1371,129 @@ static grb_info make_slices(grb_matrix A, bool in_edges) {
   return GRB_SUCCESS;
 }
 
+// ---- the hot block, per matrix (kernels and the why: batch_totals_kernel's neighbours above) -------------------------------
+// At most this many hubs (GRB_BATCH_HOT_MAX; GRB_BATCH_HOT=0: none).  Read once per process.
+constexpr long long kBatchHotMax = 64 << 10;
+static long long batch_hot_cap() {
+  static const long long cap = [] {
+    const char* on = getenv("GRB_BATCH_HOT");
+    if (on && atoi(on) == 0) return 0ll;
+    const char* e = getenv("GRB_BATCH_HOT_MAX");
+    const long long c = e ? atoll(e) : kBatchHotMax;
+    return c < 0 ? 0ll : c;
+  }();
+  return cap;
+}
+static void hot_drop(grb_matrix A) {                        // the matrix sweeps without a hot block from here on
+  BatchHot& B = A->batch_hot;
+  (void)hipStreamSynchronize(ctx().stream);
+  if (B.d_hubs) (void)hipFree(B.d_hubs);
+  if (B.d_iind) (void)hipFree(B.d_iind);
+  if (B.d_hint) (void)hipFree(B.d_hint);
+  B.d_hubs = B.d_iind = B.d_hint = nullptr;
+  B.H = 0;
+}
+// what make_hot may allocate for at most Hb hubs, scratch included
+static size_t hot_bound(grb_matrix A, long long Hb) {
+  const size_t n = (size_t)A->nrows;
+  return 4 * ((size_t)A->nvals + 1) + 4 * n + 4 * (n + 1) + 256 + device_scan_u32_scratch((long long)n + 1) + 4 * (size_t)Hb + 4 * kHotBins + 4096;
+}
+namespace {
+struct HotScratch {
+  void* p = nullptr;
+  ~HotScratch() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+static grb_info make_hot(grb_matrix A) {
+  BatchHot& B = A->batch_hot;
+  hipStream_t st = ctx().stream;
+  const Index n = A->nrows;
+  const Index* optr = A->csr.ptr;
+  // t: one more than the (cap + 1)-th largest out-degree -- the smallest threshold that leaves at most cap vertices.  Ties
+  // at that degree stay out together, so the hubs do not depend on any order among equals.
+  long long H = n;
+  B.t = 0;
+  if (B.cap < (long long)n) {
+    HotScratch bins_d;
+    GRB_HIP_TRY(hipMalloc(&bins_d.p, sizeof(unsigned int) * kHotBins));
+    std::vector<unsigned int> bins(kHotBins);
+    unsigned int mask = 0, value = 0;
+    long long rank = B.cap;                                 // of the degree looked for, from the largest, among the degrees that agree with `value` on `mask`
+    for (int shift = 2 * kHotDigitBits; shift >= 0; shift -= kHotDigitBits) {
+      GRB_HIP_TRY(hipMemsetAsync(bins_d.p, 0, sizeof(unsigned int) * kHotBins, st));
+      hipLaunchKernelGGL(batch_hot_hist_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, optr, n, mask, value, shift, (unsigned int*)bins_d.p);
+      GRB_HIP_TRY(hipGetLastError());
+      GRB_HIP_TRY(hipMemcpyAsync(bins.data(), bins_d.p, sizeof(unsigned int) * kHotBins, hipMemcpyDeviceToHost, st));
+      GRB_HIP_TRY(hipStreamSynchronize(st));
+      int digit = kHotBins - 1;
+      for (; digit > 0 && rank >= (long long)bins[digit]; --digit) rank -= (long long)bins[digit];
+      if (rank >= (long long)bins[digit]) return GRB_PANIC;  // (more than cap degrees were counted: the digit is among them)
+      value |= (unsigned int)digit << shift;
+      mask |= (unsigned int)(kHotBins - 1) << shift;
+    }
+    B.t = (long long)value + 1;
+    H = B.cap - rank;                                       // the degrees above the one selected
+  }
+  if (H <= 0 || B.t > 0x7fffffffll) return GRB_SUCCESS;
+  if ((long long)n + H > 0x7fffffffll - 64) return GRB_SUCCESS;   // a renamed index is n + slot, an Index
+  HotScratch names;
+  const size_t flag_bytes = (sizeof(unsigned int) * ((size_t)n + 1) + 255) & ~(size_t)255;
+  GRB_HIP_TRY(hipMalloc(&names.p, flag_bytes + device_scan_u32_scratch((long long)n + 1)));
+  unsigned int* const d_name = (unsigned int*)names.p;
+  hipLaunchKernelGGL(batch_hot_flag_kernel, dim3(stream_grid((long long)n + 1, kBlock)), dim3(kBlock), 0, st, optr, n, (unsigned int)B.t, d_name);
+  GRB_HIP_TRY(hipGetLastError());
+  GRB_TRY(device_exclusive_scan_u32_in(d_name, (long long)n + 1, (unsigned int*)((char*)names.p + flag_bytes)));
+  unsigned int counted = 0;
+  GRB_HIP_TRY(hipMemcpyAsync(&counted, d_name + n, sizeof(counted), hipMemcpyDeviceToHost, st));
+  GRB_HIP_TRY(hipStreamSynchronize(st));
+  if ((long long)counted != H) return GRB_PANIC;
+  GRB_HIP_TRY(hipMalloc((void**)&B.d_hubs, sizeof(Index) * (size_t)H));
+  GRB_HIP_TRY(hipMalloc((void**)&B.d_iind, sizeof(Index) * ((size_t)A->nvals + 1)));
+  GRB_HIP_TRY(hipMalloc((void**)&B.d_hint, sizeof(Index) * (size_t)n));
+  hipLaunchKernelGGL(batch_hot_names_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, optr, n, (unsigned int)B.t, d_name, B.d_hubs);
+  if (A->nvals > 0)
+    hipLaunchKernelGGL(batch_hot_rename_kernel, dim3(stream_grid(A->nvals, kBlock)), dim3(kBlock), 0, st, (const Index*)A->csc.ind,
+                       (long long)A->nvals, n, (const unsigned int*)d_name, B.d_iind);
+  hipLaunchKernelGGL(batch_hot_rename_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, (const Index*)A->d_pull_hint, (long long)n, n,
+                     (const unsigned int*)d_name, B.d_hint);
+  GRB_HIP_TRY(hipGetLastError());
+  GRB_HIP_TRY(hipStreamSynchronize(st));                    // (the name table goes when this returns)
+  B.H = (Index)H;
+  return GRB_SUCCESS;
+}
+// With the pull hint and before the sweep's sizes are taken.  Never an error: whatever stops it -- an allocation included --
+// leaves H = 0, and the matrix sweeps as it did without a hot block.  allowed = false: the caller's memory rule said no.
+static void ensure_hot(grb_matrix A, bool allowed = true) {
+  BatchHot& B = A->batch_hot;
+  if (B.ready) return;
+  B = BatchHot();
+  B.ready = true;
+  B.cap = batch_hot_cap();
+  const bool can = allowed && B.cap > 0 && A->format == 0 && !A->csc_alias && A->nrows >= 1 && A->d_pull_hint && A->csr.ptr && A->csc.ind;
+  if (can && make_hot(A) != GRB_SUCCESS) {
+    (void)hipGetLastError();
+    hot_drop(A);
+  }
+  if (getenv("GRB_BATCH_TRACE"))
+    fprintf(stderr, "sweep hot block: H %d, t %lld, cap %lld%s\n", (int)B.H, B.t, B.cap, allowed ? "" : " (no memory for it)");
+}
+
+extern "C" grb_info grb_bfs_batch_hot(grb_matrix A, long long* H, long long* t, long long* cap, grb_index* hubs, long long hubs_len) { GRB_API_ENTER();
+  if (!A) return GRB_UNINITIALIZED_OBJECT;
+  if (!A->built || !A->csr.ptr || !A->csc.ptr) return GRB_UNINITIALIZED_OBJECT;
+  if (A->nrows != A->ncols) return GRB_DIMENSION_MISMATCH;
+  GRB_TRY(ctx_init());
+  GRB_TRY(ensure_pull_hint(&A->d_pull_hint, A->csc, A->csr.ptr, ctx().stream));
+  ensure_hot(A);
+  const BatchHot& B = A->batch_hot;
+  if (H) *H = B.H;
+  if (t) *t = B.t;
+  if (cap) *cap = B.cap;
+  const long long m = std::min<long long>(B.H, hubs_len);
+  if (hubs && m > 0) GRB_HIP_TRY(hipMemcpy(hubs, B.d_hubs, sizeof(Index) * (size_t)m, hipMemcpyDeviceToHost));
+  return GRB_SUCCESS;
+}
+
 // out-edges a level may push inside the light-level launch (0: every level through the host loop)
 static long long& batch_tail_limit() {
   static long long limit = [] {
@@ -1327,6 +1523,7 @@ struct SweepOwn {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool clean_valid = false, clean[4] = {false, false, false, false};   // the rotating arrays known all-zero, for (clean_n, clean_nstore)
   Index clean_n = 0;
+  size_t clean_stride = 0;
   int clean_nstore = 0;
   bool small_clean = false;                                 // the counter slots and the big-row list's length are zero, as every complete sweep leaves them
   bool warmed = false;                                      // every batch_* kernel has been launched once ...
@@ -1335,6 +1532,7 @@ struct SweepOwn {
 SweepOwn g_sweep;
 struct SweepSizes {
   int nstore = 1;
+  size_t stride = 0;                                        // words from one array to the next: n, or n + H rounded up to 256 bytes
   size_t words = 0, tail = 0, tail_state = 0, qcap = 0, list = 0, list_ids = 0;
 };
 struct SweepTotals {                                        // the whole sweep's, as grb_bfs_batch reports them
@@ -1347,15 +1545,18 @@ u64 *g_box_h = nullptr, *g_box_d = nullptr;                 // {totals, sequence
 u64 g_box_seq = 0;
 }  // namespace
 
-static SweepSizes sweep_sizes(grb_matrix A) {
+// (H: the hot block's hubs -- the matrix's own, or a bound on them before they are known)
+static SweepSizes sweep_sizes(grb_matrix A, long long H) {
   SweepSizes z;
   const Index n = A->nrows;
+  // every array a pull can read as its frontier carries the hubs' words behind its n; seen is spaced like the rest
+  z.stride = H > 0 ? (((size_t)n + (size_t)H + 31) & ~(size_t)31) : (size_t)n;
   // stored level words: as many as fit 1 GiB, at most kBatchStoreMax (+ the seed words) + two rotating buffers
-  z.nstore = (int)((1ull << 30) / (sizeof(u64) * (size_t)(n > 0 ? n : 1)));
+  z.nstore = (int)((1ull << 30) / (sizeof(u64) * (z.stride > 0 ? z.stride : 1)));
   if (z.nstore > kBatchStoreMax) z.nstore = kBatchStoreMax;
   if (z.nstore < 1) z.nstore = 1;
   const int nbuf = 1 + (z.nstore + 1) + 4;                  // seen, the kept levels' words, four rotating arrays
-  z.words = (size_t)nbuf * sizeof(u64) * (size_t)n + 256;
+  z.words = (size_t)nbuf * sizeof(u64) * z.stride + 256;
   z.qcap = (size_t)n + (size_t)(A->nvals / kTailPiece) + 64;
   z.tail_state = (sizeof(TailState) + 255) & ~(size_t)255;
   z.tail = kTailStates * z.tail_state + 3 * sizeof(u64) * z.qcap;
@@ -1363,6 +1564,7 @@ static SweepSizes sweep_sizes(grb_matrix A) {
   z.list = kListHeader + z.list_ids + sizeof(u64) * (size_t)kListSegs * (size_t)A->batch_out.nbig;
   return z;
 }
+static SweepSizes sweep_sizes(grb_matrix A) { return sweep_sizes(A, A->batch_hot.H); }
 
 static grb_info batch_box() {
   if (g_box_h) return GRB_SUCCESS;
@@ -1383,8 +1585,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   Context& c = ctx();
   hipStream_t st = c.stream;
   const Index n = A->nrows;
-  const SweepSizes z = sweep_sizes(A);
-  const int nstore = z.nstore;
+  SweepSizes z = sweep_sizes(A);
   void *p_words, *p_cnt;
   static hipEvent_t s_ev0 = nullptr, s_ev1 = nullptr;
   hipEvent_t ev0, ev1;
@@ -1393,7 +1594,14 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     p_words = own->words; p_cnt = own->cnt;
     ev0 = own->ev0; ev1 = own->ev1;
   } else {
-    GRB_TRY(scratch(7, z.words, &p_words));
+    grb_info wi = scratch(7, z.words, &p_words);
+    if (wi != GRB_SUCCESS && A->batch_hot.H > 0) {          // no room for the tails: the sweep runs without the hot block
+      (void)hipGetLastError();
+      hot_drop(A);
+      z = sweep_sizes(A);
+      wi = scratch(7, z.words, &p_words);
+    }
+    GRB_TRY(wi);
     c.bfs_prezero_ptr = nullptr;                            // slot 7 is the one-launch traversal's pre-zeroed block
     GRB_TRY(scratch(10, sizeof(u64) * (kBatchSlots * kBatchCounters + kBatchCtlWords), &p_cnt));
     if (!s_ev0) {
@@ -1402,23 +1610,29 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     }
     ev0 = s_ev0; ev1 = s_ev1;
   }
+  const int nstore = z.nstore;
+  const size_t stride = z.stride;
+  // the hot block: H hub words behind the n of every level-word array; the pull kernels' own copies of the CSC indices and
+  // of the hint name hub j as n + j (H = 0: the matrix's arrays as they are)
+  const BatchHot& hot = A->batch_hot;
+  const Index H = hot.H;
   u64* seen = (u64*)p_words;
   // level words: slot 0 .. nstore are kept for the label pass (which level each holds is recorded as it is taken; slot 0
   // the seeds, or level 1 when the first level is the plain launch);
   // four more rotate -- a level beyond the kept ones (it labels as it discovers) and the three word arrays of the
   // light-level launch
-  auto Slot = [&](int i) -> u64* { return seen + (size_t)(1 + i) * (size_t)n; };
+  auto Slot = [&](int i) -> u64* { return seen + (size_t)(1 + i) * stride; };
   u64* const pool[4] = {Slot(nstore + 1), Slot(nstore + 2), Slot(nstore + 3), Slot(nstore + 4)};
   // known all-zero: the light-level launch leaves its arrays so, and the knowledge survives to the next sweep if nobody
   // else has had the scratch slot in between
-  static struct { bool valid = false; unsigned long long epoch = 0; void* ptr = nullptr; Index n = 0; int nstore = 0; bool clean[4]; } kept_pool;
+  static struct { bool valid = false; unsigned long long epoch = 0; void* ptr = nullptr; Index n = 0; size_t stride = 0; int nstore = 0; bool clean[4]; } kept_pool;
   bool pool_clean[4] = {false, false, false, false};
   if (own) {                                                // (nobody else ever has these buffers)
-    if (own->clean_valid && own->clean_n == n && own->clean_nstore == nstore)
+    if (own->clean_valid && own->clean_n == n && own->clean_stride == stride && own->clean_nstore == nstore)
       for (int i = 0; i < 4; ++i) pool_clean[i] = own->clean[i];
     own->clean_valid = false;
   } else {
-    if (kept_pool.valid && kept_pool.epoch + 1 == c.slot_epoch[7] && kept_pool.ptr == p_words && kept_pool.n == n && kept_pool.nstore == nstore)
+    if (kept_pool.valid && kept_pool.epoch + 1 == c.slot_epoch[7] && kept_pool.ptr == p_words && kept_pool.n == n && kept_pool.stride == stride && kept_pool.nstore == nstore)
       for (int i = 0; i < 4; ++i) pool_clean[i] = kept_pool.clean[i];
     kept_pool.valid = false;
   }
@@ -1480,7 +1694,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     if (!own) GRB_TRY(scratch(8, z.tail, &p_tail));
     GRB_HIP_TRY(hipMemsetAsync(p_tail, 0, kTailStates * z.tail_state, st));
   }
-  GRB_HIP_TRY(hipMemsetAsync(seen, 0, 2 * sizeof(u64) * (size_t)n, st));       // seen and the seeds' words
+  GRB_HIP_TRY(hipMemsetAsync(seen, 0, sizeof(u64) * (stride + (size_t)n), st));   // seen and the seeds' words (and seen's unused tail)
   SeedSources seeds;
   for (int s = 0; s < 64; ++s) seeds.v[s] = s < k ? (Index)sources[s] : 0;
 
@@ -1569,16 +1783,22 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     if (p.keep) { kept_words[nkept] = p.fnext; kept_level[nkept] = it; ++nkept; } else any_direct = true;
   };
   bool in_done = false;                                     // every big in-row has every source's bit: nothing left for the slice kernels
+  // the tail of fcur_words holds the hubs' words as they stand: a totals launch has copied them.  Not so for the seeds'
+  // words, nor for the array a light-level launch hands back: a pull of those is preceded by a copy launch of its own
+  bool tail_fresh = false;
+  const Index Hcopy = mode == GRB_PUSHONLY ? 0 : H;         // (nobody pulls: no tail is ever read)
   long long big_out_new = -1;                               // big out-rows among the frontier's vertices (-1: not counted, the light-level launch's hand-back)
   auto launch_pull = [&](BatchArgs& x) -> grb_info {
     const BatchSlices& B = A->batch_in;
     x.big = in_done ? INT_MAX : batch_big(true);
     x.slices = B.d_slices; x.nslices = B.nslices; x.bigrows = B.d_rows; x.nbig = B.nbig;
-    hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, x);
+    BatchArgs g = x;                                        // the two kernels that gather frontier words: hub j is n + j to them
+    if (H > 0) { g.iind = hot.d_iind; g.hint = hot.d_hint; }
+    hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, g);
     GRB_HIP_TRY(hipGetLastError());
     if (B.nslices > 0 && !in_done) {
       hipLaunchKernelGGL(batch_pull_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
-                         0, st, x);
+                         0, st, g);
       GRB_HIP_TRY(hipGetLastError());
       hipLaunchKernelGGL(batch_big_apply_kernel, dim3(stream_grid(B.nbig, kBlock)), dim3(kBlock), 0, st, x);
       GRB_HIP_TRY(hipGetLastError());
@@ -1700,6 +1920,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       big_out_new = -1;
       for (int i = 0; i < 3; ++i) pool_clean[xi[i]] = true;
       fcur_words = t.X[(done - 1) % 3];                     // the last level run, j = done - 1, wrote X[j % 3]
+      tail_fresh = false;
       if (status != 0) pool_clean[xi[(done - 1) % 3]] = false;   // the new frontier; every other array was left all-zero
       if (trace) {
         u64 ts[64];
@@ -1735,6 +1956,12 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     } else if (pulled_ahead) {
       // the pull kernels are already running, or done: for Q == 0 they have zeroed the words
     } else if (Q) {
+      if (H > 0 && !tail_fresh) {
+        HotCopy hc = {const_cast<u64*>(a.fcur), hot.d_hubs, n, H};
+        hipLaunchKernelGGL(batch_hot_refresh_kernel, dim3(hot_copy_blocks(H)), dim3(kBlock), 0, st, hc);
+        GRB_HIP_TRY(hipGetLastError());
+        if (trace) fprintf(stderr, "sweep hot block: level %d pulls behind a copy launch of its own\n", iter);
+      }
       GRB_TRY(launch_pull(a));
     } else if (heavy) {
       // nothing pulled, but the stash is wanted: the pull kernel's qmask == 0 path writes seen & stash where the fill
@@ -1815,8 +2042,10 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     da.iteration_left = iter + 1 <= max_niter ? 1 : 0;
     da.open_complete = P == 0 && Q != 0 ? 1 : 0;            // every live source pulled: the level's U covers them all
     da.ctl = d_ctl;
-    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, d_box, ++box_seq, da);
+    const HotCopy hc = {a.fnext, hot.d_hubs, n, Hcopy};      // the level's words are complete here: their tail, for the next level's pull
+    hipLaunchKernelGGL(batch_totals_kernel, dim3(1 + hot_copy_blocks(Hcopy)), dim3(kBlock), 0, st, a.counters, d_box, ++box_seq, da, hc);
     GRB_HIP_TRY(hipGetLastError());
+    tail_fresh = true;
     if (ahead && iter + 1 <= max_niter) {
       // the next level's pull kernels, behind the totals kernel that decides whether and on which bits they run
       BatchArgs an = a;
@@ -1884,6 +2113,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     own->small_clean = true;
     own->clean_valid = true;
     own->clean_n = n;
+    own->clean_stride = stride;
     own->clean_nstore = nstore;
     for (int i = 0; i < 4; ++i) own->clean[i] = pool_clean[i];
   } else {
@@ -1891,6 +2121,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     kept_pool.epoch = c.slot_epoch[7];
     kept_pool.ptr = p_words;
     kept_pool.n = n;
+    kept_pool.stride = stride;
     kept_pool.nstore = nstore;
     for (int i = 0; i < 4; ++i) kept_pool.clean[i] = pool_clean[i];
   }
@@ -1971,7 +2202,10 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
     DecideArgs da;
     memset(&da, 0, sizeof(da));                             // no source: the decision is "done"
     da.ctl = a.counters + kBatchSlots * kBatchCounters;
-    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, g_box_d, ++g_box_seq, da);
+    HotCopy no_hubs;
+    memset(&no_hubs, 0, sizeof(no_hubs));
+    hipLaunchKernelGGL(batch_totals_kernel, dim3(1), dim3(kBlock), 0, st, a.counters, g_box_d, ++g_box_seq, da, no_hubs);
+    hipLaunchKernelGGL(batch_hot_refresh_kernel, dim3(1), dim3(kBlock), 0, st, no_hubs);
     GRB_HIP_TRY(hipGetLastError());
     a.ctl = da.ctl;                                         // ... and the pull kernels as a launch ahead of it finds them: they leave at once
     hipLaunchKernelGGL(batch_pull_kernel, dim3(1), dim3(kBlock), 0, st, a);
@@ -2044,27 +2278,45 @@ grb_info grb::bfs_sweep_provision(grb_matrix A) {
       grow += sizeof(int) * (size_t)A->nrows;                // the table vertex -> big index
     }
   }
+  // the hot block, when this matrix has none yet: its arrays and the words' tails by the cap on the hubs.  When the rule
+  // says no to the sum but yes without them, the matrix is provisioned without a hot block.
+  const bool hot_open = !A->batch_hot.ready && batch_hot_cap() > 0;
+  bool hot_allowed = true;
   {
-    const SweepSizes zb = sweep_sizes(A);
-    if (o.words_cap < zb.words) grow += zb.words + zb.words / 8;
-    if (o.tail_cap < zb.tail) grow += zb.tail + zb.tail / 8;
+    if (o.tail_cap < sweep_sizes(A).tail) grow += sweep_sizes(A).tail + sweep_sizes(A).tail / 8;
     if (o.list_cap < list_bound) grow += list_bound + list_bound / 8;
-  }
-  if (grow > 0) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
-    if (grow + 4096 > free_b / 4) return GRB_OUT_OF_MEMORY;
+    const long long Hb = hot_open ? std::min<long long>(batch_hot_cap(), A->nrows) : (long long)A->batch_hot.H;
+    auto words_grow = [&](long long H) {
+      const size_t w = sweep_sizes(A, H).words;
+      return o.words_cap < w ? w + w / 8 : (size_t)0;
+    };
+    const size_t with_hot = grow + words_grow(Hb) + (hot_open ? hot_bound(A, Hb) : 0), without = grow + words_grow(hot_open ? 0 : Hb);
+    if (with_hot > 0) {
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return failed(GRB_OUT_OF_MEMORY);
+      if (with_hot + 4096 > free_b / 4) {
+        if (!hot_open || (without > 0 && without + 4096 > free_b / 4)) return GRB_OUT_OF_MEMORY;
+        hot_allowed = false;
+      }
+    }
   }
   grb_info i = ensure_pull_hint(&A->d_pull_hint, A->csc, A->csr.ptr, c.stream);
   if (i == GRB_SUCCESS) i = ensure_slices(A, true);
   if (i == GRB_SUCCESS) i = ensure_slices(A, false);
   if (i != GRB_SUCCESS) return failed(i);
-  const SweepSizes z = sweep_sizes(A);
+  ensure_hot(A, hot_allowed);
+  SweepSizes z = sweep_sizes(A);
   if (o.words_cap < z.words || o.tail_cap < z.tail || o.list_cap < z.list) {
     if (hipStreamSynchronize(c.stream) != hipSuccess) return failed(GRB_PANIC);   // (an earlier sweep may still read the old ones)
     o.clean_valid = false;
     o.small_clean = false;
     i = sweep_grow(&o.words, &o.words_cap, z.words);
+    if (i != GRB_SUCCESS && A->batch_hot.H > 0) {            // no room for the tails: without the hot block, then
+      (void)hipGetLastError();
+      hot_drop(A);
+      z = sweep_sizes(A);
+      i = sweep_grow(&o.words, &o.words_cap, z.words);
+    }
     if (i == GRB_SUCCESS) i = sweep_grow(&o.tail, &o.tail_cap, z.tail);
     if (i == GRB_SUCCESS) i = sweep_grow(&o.list, &o.list_cap, z.list);
     if (i != GRB_SUCCESS) return failed(i);
@@ -2111,6 +2363,7 @@ extern "C" grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_
   GRB_TRY(ensure_pull_hint(&A->d_pull_hint, A->csc, A->csr.ptr, st));
   GRB_TRY(ensure_slices(A, true));
   GRB_TRY(ensure_slices(A, false));
+  ensure_hot(A);
   SweepTotals tot;
   GRB_TRY(batch_sweep(v, k, A, sources, desc->desc[GRB_MXVMODE], desc->max_niter, desc->switchpoint, nullptr, nullptr, nullptr, &tot));
   desc->lastmxv = tot.last_dir ? GRB_PULLONLY : GRB_PUSHONLY;

@@ -657,6 +657,17 @@ struct BatchSlices {
   int nsmall = 0;
   int* d_big_index = nullptr;        // out-edges only, with the ranges: [n] vertex -> its index among the big rows (the rest never read)
 };
+// the sweep's hot block (bfs_batch.hip): the vertices of largest out-degree -- the ones most CSC entries name -- get a
+// second place for their frontier word, packed side by side behind the n words of every level-word array, and the pull
+// kernels read copies of the CSC indices and of the pull hint that name hub j as n + j
+struct BatchHot {
+  bool ready = false;            // tried: H == 0 then means this matrix sweeps without a hot block
+  Index H = 0;                   // hubs: the vertices of out-degree >= t, in ascending id; slot j is the j-th of them
+  long long t = 0, cap = 0;      // t: the smallest threshold that leaves at most cap vertices
+  Index* d_hubs = nullptr;       // [H]
+  Index* d_iind = nullptr;       // [nvals] csc.ind, hub j renamed n + j
+  Index* d_hint = nullptr;       // [n] d_pull_hint, renamed the same way
+};
 int spmv_reuse_threshold(int set);
 grb_info k_apply_unary(int dtype, int unary, int op, double scalar, const void* in, void* out, Index n);   // elementwise.hip
 // ---- lazy.hip: the queue of element-wise calls.  EVERY entry point of the C ABI starts with one of these macros:
@@ -737,6 +748,7 @@ struct grb_matrix_s {
   int* d_oc2_bigidx = nullptr;
   int oc2_nb = 0, oc2_nrows = 0, oc2_state = 0, oc2_grid = 0;
   grb::BatchSlices batch_in, batch_out;          // bfs_batch.hip, built lazily
+  grb::BatchHot batch_hot;                       // ... with them, and freed with them
   int sweep_state = 0;                           // the queue's sweep (bfs_sweep_provision): 0 not tried, 1 provisioned, -1 not for this matrix
   void* tc_prep = nullptr;                       // tc_count.hip: the degree-oriented lists of a lower triangle (built by the first count)
 };

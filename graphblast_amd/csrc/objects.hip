@@ -845,6 +845,10 @@ void grb::matrix_release_device(grb_matrix A) {
     if (b->d_big_index) (void)hipFree(b->d_big_index);
     *b = BatchSlices();
   }
+  if (A->batch_hot.d_hubs) (void)hipFree(A->batch_hot.d_hubs);
+  if (A->batch_hot.d_iind) (void)hipFree(A->batch_hot.d_iind);
+  if (A->batch_hot.d_hint) (void)hipFree(A->batch_hot.d_hint);
+  A->batch_hot = BatchHot();
   A->sweep_state = 0;
   A->nonneg_values = -1; A->mean_value = -1.0; A->small_int_values = -1;
   tc_prep_free(A);

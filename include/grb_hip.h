@@ -748,6 +748,11 @@ grb_info grb_bfs_batch(grb_vector* v, int k, grb_matrix A, const grb_index* sour
  * the tail, every level of a high-diameter graph).  0: never; < 0: only query.  Returns the previous limit
  * (default 1 Mi; GRB_BATCH_TAIL=0 / GRB_BATCH_TAIL_EDGES set it from the environment).  Same labels either way. */
 long long grb_bfs_batch_set_tail(long long edges);
+/* The hot block grb_bfs_batch and the queue's sweep keep for A (built here if A has none yet): the hubs are the vertices of
+ * out-degree >= *t, t the smallest threshold that leaves at most *cap of them (GRB_BATCH_HOT_MAX; GRB_BATCH_HOT=0: none),
+ * in ascending id.  *H receives their number (0: A sweeps without a hot block), hubs[0 .. min(H, hubs_len)) their ids;
+ * any of the pointers may be null. */
+grb_info grb_bfs_batch_hot(grb_matrix A, long long* H, long long* t, long long* cap, grb_index* hubs, long long hubs_len);
 
 /* One record per iteration of the last grb_sssp / grb_pr / grb_cc call on a descriptor: what the
  * reference's drivers print per iteration under --timing 1 (sssp.hpp:55-62, pr.hpp:53-62) or 2
