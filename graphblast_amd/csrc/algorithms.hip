@@ -204,8 +204,7 @@ __global__ __launch_bounds__(kBlock) void pr_update_kernel(const float* __restri
   if (threadIdx.x == 0) {
     float tot = 0.f;
     for (int w = 0; w < kWavesPerBlock; ++w) tot += s_sum[w];
-    __hip_atomic_store(&mail[0], ((unsigned long long)(unsigned int)seq << 32) | __float_as_uint(tot),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    mail_granule(&mail[0], seq, __float_as_uint(tot));
   }
 }
 }  // namespace grb
@@ -305,9 +304,7 @@ __global__ __launch_bounds__(kPThreads) void cc_tail_kernel(int* __restrict__ mn
   }
   unsigned gen = gen0;
   if (!grid_sync(bar, gen, true)) {
-    if (gtid == 0)
-      __hip_atomic_store(&mail[0], ((unsigned long long)(unsigned int)seq << 32) | 0xffffffffull, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_SYSTEM);
+    if (gtid == 0) mail_granule(&mail[0], seq, 0xffffffffu);
     return;
   }
   unsigned int cnt = 0;
@@ -344,8 +341,7 @@ __global__ __launch_bounds__(kPThreads) void cc_tail_kernel(int* __restrict__ mn
     unsigned int tot = 0;
     for (int w = 0; w < kPWaves; ++w) tot += s_cnt[w];
     if (tot == 0xffffffffu) tot = 0xfffffffeu;            // 0xffffffff is the barrier's distress value
-    __hip_atomic_store(&mail[0], ((unsigned long long)(unsigned int)seq << 32) | tot, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
+    mail_granule(&mail[0], seq, tot);
   }
 }
 }  // namespace grb

@@ -690,7 +690,7 @@ grb_info bcc_run(grb_matrix C, grb_vector art, grb_matrix A, int mode, grb_bcc_r
   const bool both = C && C->format != 1;
   grb_bcc_result r = {};
   Side sr, sc;
-  if (n > 0) GRB_TRY(persistent_kernel_fits(bcc_persistent_kernel));
+  if (n > 0) GRB_TRY(persistent_kernel_fits<bcc_persistent_kernel>());
   EventPair ev;
   GRB_TRY(ev.create());
   // ---- one allocation: the state, sixteen words per vertex (lvoff has n + 2), the representatives' pairs, the scan's totals

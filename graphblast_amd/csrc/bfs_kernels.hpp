@@ -203,12 +203,9 @@ static __global__ __launch_bounds__(kBlock) void bfs_level_tail_kernel(
     const unsigned long long acc = *edges_acc + d2;
     *edges_acc = acc;
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long tag = (unsigned long long)(unsigned int)seq << 32;
     const unsigned int vals[6] = {(unsigned int)c2, (unsigned int)d_state[1], (unsigned int)(acc & 0xffffffffull),
                                   (unsigned int)(acc >> 32), (unsigned int)d_state[2], (unsigned int)d_state[3]};
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-      __hip_atomic_store(&mail[k], tag | vals[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    mail_granules(mail, seq, vals);
   }
 }
 

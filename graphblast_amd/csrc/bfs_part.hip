@@ -127,8 +127,7 @@ __global__ __launch_bounds__(kBlock) void bfs_part_apply2_kernel(
     for (int k = 0; k < 3; ++k) {
       unsigned int t = 0;
       for (int w = 0; w < kWavesPerBlock; ++w) t += smem[k][w];
-      __hip_atomic_store(&mail[k], ((unsigned long long)(unsigned int)seq << 32) | t, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_SYSTEM);
+      mail_granule(&mail[k], seq, t);
     }
   }
 }

@@ -23,16 +23,14 @@
 // travel from launch to launch in device memory.  The host enqueues launch k + 1 when launch k - 1 has
 // reported (one word in pinned memory, polled -- the device always has a launch queued and never waits for
 // the host); that rule depends only on values every rank computes identically, so all ranks enqueue the same
-// number of collectives.  A launch that finds the traversal finished exits at once; one launch and one
+// number of collectives (the rule and the word: part_driver.hpp; the mailbox: part_common.hpp).  A launch that finds the traversal finished exits at once; one launch and one
 // collective at most are spent after the end.  With one rank and levels_per_launch > 1 the same kernel runs
 // several levels per launch (there is no collective to wait for).
 //
 // The reference has nothing to mirror (--ndevice is parsed and ignored, backend/cuda/descriptor.hpp:242);
 // results are those of algorithm::bfs (graphblas/algorithm/bfs.hpp:14-89) on the whole graph.
 #include "bfs_kernels.hpp"
-#include "persist_common.hpp"
-
-#include <chrono>
+#include "part_common.hpp"
 
 namespace grb {
 
@@ -169,15 +167,11 @@ __global__ __launch_bounds__(kPThreads) void bfs_part_level_kernel(PartArgs a) {
     cy = st->carry[k & 1];
   }
   const bool panicked = fresh(&st->panic[0]) != 0u;
-  auto report = [&](const PartCarry& y, bool bad) {   // one 8-byte word: the data is the flag
-    const unsigned long long hi = bad ? 0xffffffffull : (unsigned long long)(unsigned)(y.done_at + 1);
-    __hip_atomic_store(a.mail, (hi << 32) | (unsigned long long)(unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  };
   if (cy.done || panicked) {                           // the traversal ended in an earlier launch: hand the scalars on
     if (gtid == 0) {
       st->carry[(k + 1) & 1] = cy;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      report(cy, panicked);
+      part_report(a.mail, k, cy, panicked);
     }
     return;
   }
@@ -643,7 +637,7 @@ incl = (int)wave_incl_scan_u32((unsigned)incl);
     st->carry[(k + 1) & 1] = cy;
     if (cy.done) *a.result = cy;                            // pinned host memory: read after the final synchronisation
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    report(cy, false);
+    part_report(a.mail, k, cy, false);
   }
 }
 
@@ -668,22 +662,6 @@ __global__ __launch_bounds__(kBlock) void bfs_part_hint_kernel(const Index* __re
       if (od > wd || (od == wd && ob >= 0 && (wb < 0 || ob < wb))) { wd = od; wb = ob; }
     }
     if (lane == 0) hint[v] = wb;
-  }
-}
-
-// grb_bfs_part_run_group's stand-in for the all-gather: every rank's send buffer into slot r of every rank's
-// receive buffer, one launch (all ranks live on this device)
-constexpr int kLoopMaxRanks = 16;
-struct LoopbackPtrs {
-  const unsigned int* send[kLoopMaxRanks];
-  unsigned int* recv[kLoopMaxRanks];
-};
-__global__ __launch_bounds__(kBlock) void loopback_allgather_kernel(LoopbackPtrs p, int world, int nwords) {
-  const long long total = (long long)world * nwords;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < total; i += (long long)gridDim.x * kBlock) {
-    const int r = (int)(i / nwords);
-    const unsigned int x = p.send[r][i - (long long)r * nwords];
-    for (int q = 0; q < world; ++q) p.recv[q][i] = x;
   }
 }
 
@@ -713,9 +691,7 @@ struct grb_part_s {
   bool prezeroed = false;               // the zeroed part of d_block was cleared behind the previous traversal
   Index* d_hint = nullptr;
   long long n_in_local = -1;            // owned vertices with in-edges
-  unsigned long long* h_mail = nullptr;   // pinned
-  unsigned long long* d_mail = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  PartMail mail;
 };
 
 namespace {
@@ -731,14 +707,6 @@ PartPtrs part_ptrs(grb_part p) {
   q.Fn = q.V + p->nwords;
   q.F = q.Fn + p->nwords;
   return q;
-}
-
-// launches that have reported, and the launch that ended the traversal (-1: none yet; -2: a barrier gave up)
-void mail_peek(grb_part p, int* launches_done, int* done_at) {
-  const unsigned long long g = __atomic_load_n(p->h_mail, __ATOMIC_ACQUIRE);
-  *launches_done = (int)(g & 0xffffffffull);
-  const unsigned int hi = (unsigned int)(g >> 32);
-  *done_at = hi == 0xffffffffu ? -2 : (int)hi - 1;
 }
 
 // One traversal over `nranks` rank contexts driven in lock-step on this device.  nranks == 1 is a real run
@@ -757,18 +725,10 @@ grb_info part_bfs_run(grb_part* ps, int nranks, grb_index source, int mode, floa
   LoopbackPtrs loop_ptrs = {};
   if (source < 0 || source >= p0->n) return GRB_INVALID_INDEX;
   if (mode != GRB_PUSHPULL && mode != GRB_PUSHONLY && mode != GRB_PULLONLY) return GRB_INVALID_VALUE;
-  if (!loopback && world > 1) {
-    int r = -1, w = 0;
-    grb_comm_info(&r, &w);
-    if (w != world || r != p0->rank) return GRB_UNINITIALIZED_OBJECT;
-  }
+  if (!loopback && world > 1 && !part_comm_matches(p0->rank, world)) return GRB_UNINITIALIZED_OBJECT;
   if (world > 1 || levels_per_launch < 1) levels_per_launch = 1;
   GRB_TRY(bfs_lanes_fence(ctx().stream));   // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, bfs_part_level_kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
-  }
+  GRB_TRY(persistent_kernel_fits<bfs_part_level_kernel>());
   const int G = c.num_cu;
 
   std::vector<PartArgs> args(nranks);
@@ -800,9 +760,9 @@ grb_info part_bfs_run(grb_part* ps, int nranks, grb_index source, int mode, floa
     a.oc_nb = p->oc_nb; a.oc_nrows = p->oc_nrows;
     a.st = q.st;
     a.rec = p->d_rec; a.rec_cap = p->rec_cap;
-    a.mail = p->d_mail;
-    a.result = reinterpret_cast<PartCarry*>(p->d_mail + 8);
-    __atomic_store_n(p->h_mail, 0ull, __ATOMIC_RELEASE);   // nothing of this device is in flight: every run ends synchronised
+    a.mail = p->mail.d_mail;
+    a.result = p->mail.d_carry<PartCarry>();
+    p->mail.reset();
     a.launch = 0;
     a.nlevels = levels_per_launch;
     // zeroed: the state, V, Fn and F[0]; the other level bitmaps are written in full before they are read
@@ -810,60 +770,31 @@ grb_info part_bfs_run(grb_part* ps, int nranks, grb_index source, int mode, floa
     p->prezeroed = false;
     if (loopback) { loop_ptrs.send[r] = q.Fn; loop_ptrs.recv[r] = p->d_gathered; }
   }
-  const auto t0 = std::chrono::steady_clock::now();
-  GRB_HIP_TRY(hipEventRecord(p0->ev0, s));
   int k = 0;
   const size_t bm_bytes = 4 * (size_t)p0->nwords;
   const bool one_shot = world == 1 && levels_per_launch > max_niter;   // the first launch runs every level
-  for (;;) {
-    // Launch k goes out when launch k - 2 has reported and had not ended the traversal: the device always has
-    // launch k - 1 queued behind it.  The rule reads only what launch k - 2 computed -- the same on every rank --
-    // so every rank enqueues the same number of launches and collectives: (the ending launch's index) + 2.
-    if (k >= 2) {
-      unsigned spins = 0;
-      bool synced = false;
-      int ld = 0, done_at = -1;
-      for (;;) {
-        mail_peek(p0, &ld, &done_at);
-        if (ld >= k - 1) break;
-        if ((++spins & 4095u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-          if (synced) return GRB_PANIC;
-          GRB_HIP_TRY(hipStreamSynchronize(s));
-          synced = true;
-        }
-      }
-      if (done_at == -2) return GRB_PANIC;
-      if (done_at >= 0 && done_at <= k - 2) break;
-    }
+  auto enqueue = [&](int launch) -> grb_info {         // launch `launch` of every rank, and its exchange
     for (int r = 0; r < nranks; ++r) {
-      args[r].launch = k;
+      args[r].launch = launch;
       hipLaunchKernelGGL(bfs_part_level_kernel, dim3(G), dim3(kPThreads), 0, s, args[r]);
       GRB_HIP_TRY(hipGetLastError());
     }
     if (loopback) {
-      hipLaunchKernelGGL(loopback_allgather_kernel, dim3(stream_grid((long long)nranks * p0->nwords)), dim3(kBlock), 0, s,
-                         loop_ptrs, nranks, p0->nwords);
-      GRB_HIP_TRY(hipGetLastError());
+      GRB_TRY(loopback_allgather(loop_ptrs, nranks, p0->nwords, s));
     } else if (world > 1) {
       GRB_TRY(grb_comm_allgather(args[0].Fn, p0->d_gathered, bm_bytes));
       GRB_TRY(grb_comm_wait());
     }
-    ++k;
-    if (one_shot) break;
-    if (k > (1 << 28)) return GRB_PANIC;
-  }
+    return GRB_SUCCESS;
+  };
+  GRB_TRY(p0->mail.drive(s, enqueue, 20, one_shot, &k));
   // k launches went out; the one that ended the traversal wrote the labels and left the scalars in pinned memory
-  GRB_HIP_TRY(hipEventRecord(p0->ev1, s));
-  GRB_HIP_TRY(hipEventSynchronize(p0->ev1));
   float ms = 0.f;
-  GRB_HIP_TRY(hipEventElapsedTime(&ms, p0->ev0, p0->ev1));
+  GRB_TRY(p0->mail.elapsed_ms(s, &ms));
   for (int r = 0; r < nranks; ++r) {
     grb_part p = ps[r];
-    int ld = 0, done_at = -1;
-    mail_peek(p, &ld, &done_at);
     PartCarry cy;
-    memcpy(&cy, p->h_mail + 8, sizeof(cy));
-    if (done_at < 0 || !cy.done) return GRB_PANIC;          // -2: a grid barrier gave up
+    GRB_TRY(p->mail.read_carry(&cy));
     if (res) {
       res[r].levels = cy.levels;
       res[r].launches = k;
@@ -927,11 +858,7 @@ grb_info grb_part_new(grb_part* out, int rank, int world, grb_index n_global, gr
   }
   if (hipHostMalloc((void**)&p->h_rec, sizeof(grb_bfs_level) * (size_t)p->rec_cap, hipHostMallocMapped) != hipSuccess) return fail(GRB_OUT_OF_MEMORY);
   if (hipHostGetDevicePointer((void**)&p->d_rec, p->h_rec, 0) != hipSuccess) return fail(GRB_PANIC);
-  if (hipHostMalloc((void**)&p->h_mail, 256, hipHostMallocMapped) != hipSuccess) return fail(GRB_OUT_OF_MEMORY);
-  memset(p->h_mail, 0, 256);
-  static_assert(sizeof(PartCarry) <= 256 - 64, "the result record follows the mail word in pinned memory");
-  if (hipHostGetDevicePointer((void**)&p->d_mail, p->h_mail, 0) != hipSuccess) return fail(GRB_PANIC);
-  if (hipEventCreate(&p->ev0) != hipSuccess || hipEventCreate(&p->ev1) != hipSuccess) return fail(GRB_PANIC);
+  if (const grb_info mi = p->mail.create()) return fail(mi);
   if (ensure_empty_rows(&A_in->d_empty_csr_rows, A_in->csr, s) != GRB_SUCCESS) return fail(GRB_PANIC);
   if (p->n_local > 0) {
     if (hipMalloc((void**)&p->d_hint, 4 * (size_t)p->n_local) != hipSuccess) return fail(GRB_OUT_OF_MEMORY);
@@ -964,9 +891,7 @@ grb_info grb_part_free(grb_part p) { GRB_API_ENTER();
   if (p->d_oc_bigidx) (void)hipFree(p->d_oc_bigidx);
   if (p->h_rec) (void)hipHostFree(p->h_rec);
   if (p->d_hint) (void)hipFree(p->d_hint);
-  if (p->h_mail) (void)hipHostFree(p->h_mail);
-  if (p->ev0) (void)hipEventDestroy(p->ev0);
-  if (p->ev1) (void)hipEventDestroy(p->ev1);
+  p->mail.destroy();
   delete p;
   return GRB_SUCCESS;
 }

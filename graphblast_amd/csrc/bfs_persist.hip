@@ -989,6 +989,7 @@ incl = (int)wave_incl_scan_u32((unsigned)incl);
     next = (int)fresh(&st->next_idx[0]);
   }
   if (gtid == 0) {
+    // mail_granules (common.hpp) written out: through the helper this kernel's instructions reorder
     const unsigned long long tag = (unsigned long long)(unsigned int)ph(tp)->seq << 32;
     const float ms = (float)(wall_clock64() - t_start) * a.ticks_to_ms;
     const unsigned int vals[8] = {(unsigned int)levels, (unsigned int)last_dir, (unsigned int)reached,
@@ -1567,11 +1568,8 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
   const int nwords = z.nwords;
   int wgs_per_cu = 1;
   if (const char* e = getenv("GRB_BFS_WGS_PER_CU")) wgs_per_cu = atoi(e) >= 2 ? 2 : 1;
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, bfs_persistent_kernel<kPThreads>, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
-  }
+  int max_per_cu = 0;
+  GRB_TRY(persistent_kernel_fits<bfs_persistent_kernel<kPThreads>>(&max_per_cu));
   if (wgs_per_cu > max_per_cu) wgs_per_cu = max_per_cu;
   const int G_full = c.num_cu * wgs_per_cu;
   // lanes > 1: a queued traversal takes its share of the CUs (the blocking call, lane 0 alone, the whole device);
@@ -1601,14 +1599,6 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
   } else {
     p_zero = ln.zero; p_v1 = ln.v1; p_big = ln.big; p_rec = ln.rec;
     ln.clean_bytes = 0;
-  }
-
-  static float ticks_to_ms = 0.f;
-  if (ticks_to_ms == 0.f) {
-    int khz = 0, dev = 0;
-    GRB_HIP_TRY(hipGetDevice(&dev));
-    GRB_HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-    ticks_to_ms = khz > 0 ? 1.0f / (float)khz : 1e-5f;
   }
 
   PersistArgs& a = *out;
@@ -1699,7 +1689,7 @@ static grb_info bfs_persistent_args(grb_matrix A, const BfsRules& rules, int pro
   }
   gout->rec = (grb_bfs_level*)p_rec;
   a.rec_cap = co ? 0 : rec_cap;                              // (per-level records: the blocking call's profiling runs read them)
-  a.ticks_to_ms = ticks_to_ms;
+  GRB_TRY(wall_ticks_to_ms(&a.ticks_to_ms));
   *p_rec_out = p_rec;
   *trace_out = nullptr;
   static const bool want_trace = getenv("GRB_BFS_TRACE") != nullptr;
@@ -1985,10 +1975,9 @@ static grb_info bfs_persistent_collect(int slot, int seq, int profile, void* p_r
   *tight_ms = ms;
   if (trace) {
     unsigned long long h[256];
-    int khz = 0, dev = 0;
-    GRB_HIP_TRY(hipGetDevice(&dev));
-    GRB_HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-    const double tick_us = khz > 0 ? 1e3 / (double)khz : 1e-2;
+    float tick_ms = 0.f;
+    GRB_TRY(wall_ticks_to_ms(&tick_ms));
+    const double tick_us = 1e3 * (double)tick_ms;
     GRB_HIP_TRY(hipMemcpyAsync(h, trace, sizeof(h), hipMemcpyDeviceToHost, s));
     GRB_HIP_TRY(hipStreamSynchronize(s));
     fprintf(stderr, "bfs trace (us since kernel start; init, then per level: expanded / barrier / totals):");

@@ -420,6 +420,21 @@ __device__ inline bool last_workgroup_arrives(unsigned int* tickets) {
   return true;
 }
 
+// ---- the granule mailbox: a kernel's last few scalars, read by the host without a copy or a synchronisation.  A granule
+// is one 8-byte word of pinned memory, seq << 32 | value: the tag travels WITH its value, so there is no flag and no fence.
+//   device   granule k = seq << 32 | vals[k], each ONE relaxed system-scope store, by one thread as the kernel's last act
+//   host     wait_granules spins until granules [0, count) all carry the tag `seq` (the call's number, Context::mail_seq),
+//            values -> out; after 5 ms one wait for the stream, then GRB_PANIC if they still do not (objects.hip)
+__device__ __forceinline__ void mail_granule(unsigned long long* granule, unsigned int seq, unsigned int val) {
+  __hip_atomic_store(granule, ((unsigned long long)seq << 32) | val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+template <int N>
+__device__ __forceinline__ void mail_granules(unsigned long long* mail, unsigned int seq, const unsigned int (&vals)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) mail_granule(&mail[k], seq, vals[k]);
+}
+grb_info wait_granules(int seq, int count, unsigned int* out);
+
 // The part of a one-launch reduction that follows every thread's private fold (elementwise.hip: reduce_kernel;
 // lazy.hip: a chain of element-wise calls whose last result is reduced in the same launch -- the SAME association
 // order, so the value does not depend on which of the two ran): butterfly inside the wave, the waves in order, the
@@ -460,7 +475,7 @@ __device__ inline void reduce_finish(T acc, F add, T identity, unsigned int* par
   if (threadIdx.x == 0) {
     unsigned int t = smem[0];
     for (int w = 1; w < kWavesPerBlock; ++w) t = bits(add(from(t), from(smem[w])));
-    __hip_atomic_store(&mail[0], ((unsigned long long)(unsigned int)seq << 32) | t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    mail_granule(&mail[0], seq, t);
   }
 }
 
@@ -551,8 +566,6 @@ grb_info scratch(int i, size_t bytes, void** out);
 grb_info fetch_ints(const int* d_src, int count, int* h_dst);
 // Host side of an in-kernel mailbox publish: wait until h_mail[63] == seq.
 grb_info wait_mail(int seq);
-// Wait until granules [0, count) of the granule mailbox carry tag `seq`; values -> out.
-grb_info wait_granules(int seq, int count, unsigned int* out);
 
 // ----------------------------------------------------------------------------
 // Objects behind the handles

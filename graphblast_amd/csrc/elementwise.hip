@@ -329,8 +329,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(const T* __restrict__ d,
       if constexpr (kCountNeq) t += smem[w];
       else t = bits(Mo::add(from(t), from(smem[w])));
     }
-    __hip_atomic_store(&mail[0], ((unsigned long long)(unsigned int)seq << 32) | t, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
+    mail_granule(&mail[0], seq, t);
   }
 }
 

@@ -1,7 +1,7 @@
 // graph_common.hpp -- the helpers the graph algorithms share (ktruss, bc, cdlp, lcc, kcore, scc, msf, matching, contract,
 // maxflow, bcc): searches in a row, the order of weights, the structural-symmetry check, a wave's staged appends, the split
 // of a row into 16-byte quads, the weight sum's fixed-order tail; and on the host the event pair, padding, result arrays,
-// the occupancy check and the dense output vector.  The tuning constants (k*LaneLen, k*WaveLen, k*Stage), the row dealers
+// and the dense output vector (the occupancy check: persist_common.hpp).  The tuning constants (k*LaneLen, k*WaveLen, k*Stage), the row dealers
 // and the persistent kernels' bodies stay in their files: each algorithm is retuned alone.
 #pragma once
 #include "persist_common.hpp"
@@ -184,17 +184,6 @@ inline grb_info side_mirror(Side* csc, const Side& csr, Index n, long long m, hi
   if (m > 0) {
     GRB_HIP_TRY(hipMemcpyAsync(csc->ind.p, csr.ind.p, 4 * (size_t)m, hipMemcpyDeviceToDevice, s));
     GRB_HIP_TRY(hipMemcpyAsync(csc->val.p, csr.val.p, 4 * (size_t)m, hipMemcpyDeviceToDevice, s));
-  }
-  return GRB_SUCCESS;
-}
-
-// the one-launch kernel fits: a 1024-thread workgroup of it can be resident on a CU.  Asked once per process and kernel.
-template <typename K>
-static grb_info persistent_kernel_fits(K kernel) {
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
   }
   return GRB_SUCCESS;
 }

@@ -311,7 +311,7 @@ grb_info kcore_run(grb_vector out, grb_matrix A, int k, grb_kcore_result* res) {
   Context& c = ctx();
   hipStream_t s = c.stream;
   const Index n = A->nrows;
-  GRB_TRY(persistent_kernel_fits(kcore_persistent_kernel));
+  GRB_TRY(persistent_kernel_fits<kcore_persistent_kernel>());
   EventPair ev;
   GRB_TRY(ev.create());
   // ---- one allocation: the state, deg, order

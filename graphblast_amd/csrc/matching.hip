@@ -457,7 +457,7 @@ grb_info matching_run(grb_vector mate, grb_matrix C, grb_matrix A, int mode, uns
   const bool both = C && C->format != 1;
   grb_matching_result r = {};
   Side sr, sc;
-  if (n > 0) GRB_TRY(persistent_kernel_fits(matching_persistent_kernel));
+  if (n > 0) GRB_TRY(persistent_kernel_fits<matching_persistent_kernel>());
   EventPair ev;
   GRB_TRY(ev.create());
   // ---- one allocation: the state, six words per vertex (mate, cand, cpos, queue, list, the flags of the scan), the scan's

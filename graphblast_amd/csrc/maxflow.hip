@@ -792,7 +792,7 @@ grb_info maxflow_run(grb_matrix F, grb_vector side, grb_matrix A, Index source, 
   const bool both = F && F->format != 1;
   grb_maxflow_result r = {};
   Side sr, sc;
-  GRB_TRY(persistent_kernel_fits(maxflow_persistent_kernel));
+  GRB_TRY(persistent_kernel_fits<maxflow_persistent_kernel>());
   EventPair ev;
   GRB_TRY(ev.create());
   // ---- one allocation: the state; per vertex the row pointers, excess, received, two heights, stamp, two queues, receivers;

@@ -518,7 +518,7 @@ grb_info msf_run(grb_matrix C, grb_vector comp, grb_matrix A, grb_msf_result* re
   const bool both = C->format != 1;
   grb_msf_result r = {};
   Side sr, sc;
-  if (n > 0) GRB_TRY(persistent_kernel_fits(msf_persistent_kernel));
+  if (n > 0) GRB_TRY(persistent_kernel_fits<msf_persistent_kernel>());
   EventPair ev;
   GRB_TRY(ev.create());
   // ---- one allocation: the state, best (8 bytes), six words per vertex, then the pairs of both directions and the partial sums

@@ -170,6 +170,34 @@ incl = (int)wave_incl_scan_u32((unsigned)incl);
   __builtin_amdgcn_wave_barrier();
 }
 
+// ---- host: what every one-launch driver asks before its launch ------------------------------------------------------------
+// The kernel fits: a 1024-thread workgroup of it can be resident on a CU (*per_cu: how many).  Asked once per process and
+// kernel -- the cache belongs to the kernel itself, not to its type.  `unfit` when it does not fit: GRB_PANIC, or
+// GRB_NOT_IMPLEMENTED where the caller has another way.
+template <auto Kernel>
+static grb_info persistent_kernel_fits(int* per_cu = nullptr, grb_info unfit = GRB_PANIC) {
+  static int max_per_cu = 0;
+  if (!max_per_cu) {
+    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, Kernel, kPThreads, 0));
+    if (max_per_cu < 1) return unfit;
+  }
+  if (per_cu) *per_cu = max_per_cu;
+  return GRB_SUCCESS;
+}
+
+// milliseconds per tick of wall_clock64(), for the kernels that time themselves.  Asked once per process.
+inline grb_info wall_ticks_to_ms(float* out) {
+  static float ticks_to_ms = 0.f;
+  if (ticks_to_ms == 0.f) {
+    int khz = 0, dev = 0;
+    GRB_HIP_TRY(hipGetDevice(&dev));
+    GRB_HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
+    ticks_to_ms = khz > 0 ? 1.0f / (float)khz : 1e-5f;
+  }
+  *out = ticks_to_ms;
+  return GRB_SUCCESS;
+}
+
 
 struct __attribute__((packed, aligned(4))) Quad { Index x, y, z, w; };   // four consecutive column ids
 #ifndef GRB_SPARSE_WORDS

@@ -501,7 +501,7 @@ grb_info scc_run(grb_vector out, grb_matrix A, grb_scc_result* res) {
   Context& c = ctx();
   hipStream_t s = c.stream;
   const Index n = A->nrows;
-  GRB_TRY(persistent_kernel_fits(scc_persistent_kernel));
+  GRB_TRY(persistent_kernel_fits<scc_persistent_kernel>());
   EventPair ev;
   GRB_TRY(ev.create());
   // ---- one allocation: the state, then six arrays of a word per vertex

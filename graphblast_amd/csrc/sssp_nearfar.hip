@@ -234,6 +234,7 @@ __global__ __launch_bounds__(kPThreads) void sssp_nearfar_kernel(NfArgs a) {
   if (lane == 0 && md) atomicMax(&st->maxdist[0], md);
   if (!grid_sync(&st->bar, gen, false)) return;
   if (gtid == 0) {
+    // mail_granules (common.hpp) written out: through the helper this kernel's instructions reorder
     const u64 tag = (u64)(unsigned int)a.seq << 32;
     const float ms = (float)(wall_clock64() - t_start) * a.ticks_to_ms;
     const unsigned int vals[8] = {fresh(&st->maxhops[0]), (unsigned int)pass, __float_as_uint(ms), (unsigned int)converged,
@@ -606,6 +607,7 @@ __global__ __launch_bounds__(kPThreads) void sssp_nfq_kernel(NfqArgs a) {
   unsigned int unused;
   if (!nfq_sync(st, bidx++, &unused)) return;
   if (gtid == 0) {
+    // mail_granules (common.hpp) written out: through the helper this kernel's instructions reorder
     const u64 tag = (u64)(unsigned int)a.seq << 32;
     const float ms = (float)(wall_clock64() - t_start) * a.ticks_to_ms;
     u64 c0 = fresh(&st->work[0][0]), c1 = fresh(&st->work[1][0]) >> 4;
@@ -719,21 +721,8 @@ grb_info grb::sssp_nearfar_run(grb_vector v, grb_matrix A, grb_index source, grb
   }
   const int nwords = 2 * ceil_div(n, 64);
   GRB_TRY(bfs_lanes_fence(ctx().stream));   // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    int m2 = 0;
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, sssp_nearfar_kernel, kPThreads, 0));
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&m2, sssp_nfq_kernel, kPThreads, 0));
-    if (m2 < max_per_cu) max_per_cu = m2;
-    if (max_per_cu < 1) return GRB_NOT_IMPLEMENTED;
-  }
-  static float ticks_to_ms = 0.f;
-  if (ticks_to_ms == 0.f) {
-    int khz = 0, dev = 0;
-    GRB_HIP_TRY(hipGetDevice(&dev));
-    GRB_HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-    ticks_to_ms = khz > 0 ? 1.0f / (float)khz : 1e-5f;
-  }
+  GRB_TRY(persistent_kernel_fits<sssp_nearfar_kernel>(nullptr, GRB_NOT_IMPLEMENTED));
+  GRB_TRY(persistent_kernel_fits<sssp_nfq_kernel>(nullptr, GRB_NOT_IMPLEMENTED));
   // the band: GRB_SSSP_DELTA x the mean edge weight.  Measured flat from 32 to 128 for the queue form (85-88 ms on
   // the road-like stand-in: fewer passes, each a little longer) and from 16 to 64 for the bitmap form
   static const double delta_env = getenv("GRB_SSSP_DELTA") ? atof(getenv("GRB_SSSP_DELTA")) : 0.0;
@@ -776,7 +765,7 @@ grb_info grb::sssp_nearfar_run(grb_vector v, grb_matrix A, grb_index source, grb
     a.D = (float*)v->d_val;
     a.mail = c.d_hgran;
     a.seq = seq = ++c.mail_seq;
-    a.ticks_to_ms = ticks_to_ms;
+    GRB_TRY(wall_ticks_to_ms(&a.ticks_to_ms));
     a.max_passes = max_passes;
     a.unit = 0;
     a.as_bfs = 0;
@@ -805,7 +794,7 @@ grb_info grb::sssp_nearfar_run(grb_vector v, grb_matrix A, grb_index source, grb
     a.D = (float*)v->d_val;
     a.mail = c.d_hgran;
     a.seq = seq = ++c.mail_seq;
-    a.ticks_to_ms = ticks_to_ms;
+    GRB_TRY(wall_ticks_to_ms(&a.ticks_to_ms));
     a.max_passes = max_passes;
     static const int inner = getenv("GRB_SSSP_INNER") ? atoi(getenv("GRB_SSSP_INNER")) : 2;
     a.inner = inner < 1 ? 1 : inner;
@@ -864,18 +853,7 @@ grb_info grb::bfs_queue_run(grb_vector v, grb_matrix A, grb_index source, grb_de
   Context& c = ctx();
   hipStream_t s = c.stream;
   GRB_TRY(bfs_lanes_fence(ctx().stream));   // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, sssp_nfq_kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_NOT_IMPLEMENTED;
-  }
-  static float ticks_to_ms = 0.f;
-  if (ticks_to_ms == 0.f) {
-    int khz = 0, dev = 0;
-    GRB_HIP_TRY(hipGetDevice(&dev));
-    GRB_HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-    ticks_to_ms = khz > 0 ? 1.0f / (float)khz : 1e-5f;
-  }
+  GRB_TRY(persistent_kernel_fits<sssp_nfq_kernel>(nullptr, GRB_NOT_IMPLEMENTED));
   const size_t st_bytes = (sizeof(NfqState) + 255) & ~(size_t)255;
   const size_t near_cap = (size_t)n + 64, far_cap = 64;   // a vertex is queued once (its first key is its last); nothing is far
   void *p_zero, *p_k, *p_q;
@@ -895,7 +873,7 @@ grb_info grb::bfs_queue_run(grb_vector v, grb_matrix A, grb_index source, grb_de
   a.D = (float*)v->d_val;
   a.mail = c.d_hgran;
   a.seq = ++c.mail_seq;
-  a.ticks_to_ms = ticks_to_ms;
+  GRB_TRY(wall_ticks_to_ms(&a.ticks_to_ms));
   const long long pass_cap = (long long)n + 1024;
   a.max_passes = pass_cap > 0x7fffff00ll ? 0x7fffff00 : (int)pass_cap;
   a.unit = 1;

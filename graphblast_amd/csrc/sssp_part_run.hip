@@ -21,14 +21,12 @@
 // (vertex, edge offset), the rank reports "not finished" in its header, and the next launch continues the SAME round
 // from those points while the other ranks only apply -- so the number of rounds, and the distances after each, are
 // the reference's whatever the capacity.  Termination lags one exchange (the improved counts travel in the headers);
-// the host-side launch rule is grb_bfs_part_run's: launch k goes out when launch k - 2 has reported, every rank
-// enqueues the same number of collectives.  With one rank several rounds run per launch.
+// the host-side launch rule is grb_bfs_part_run's (part_driver.hpp): launch k goes out when launch k - 2 has reported,
+// every rank enqueues the same number of collectives.  With one rank several rounds run per launch.
 //
 // Weights must be non-negative (distances compare as unsigned integers in the atomics), as for grb_sssp's persistent
 // kernel.  The reference has no multi-GPU code (backend/cuda/descriptor.hpp:242).
-#include "persist_common.hpp"
-
-#include <chrono>
+#include "part_common.hpp"
 
 namespace grb {
 
@@ -98,10 +96,6 @@ __global__ __launch_bounds__(kPThreads) void sssp_part_kernel(SsspArgs a) {
     for (int i = tid; i < (int)(sizeof(GridBarrier) / sizeof(unsigned)); i += kPThreads) publish(&z[i], 0u);
   }
   SsspCarry cy = st->carry[k & 1];
-  auto report = [&](const SsspCarry& y, bool bad) {
-    const unsigned long long hi32 = bad ? 0xffffffffull : (unsigned long long)(unsigned)(y.done_at + 1);
-    __hip_atomic_store(a.mail, (hi32 << 32) | (unsigned long long)(unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  };
   const bool panicked = fresh(&st->panic[0]) != 0u;
   if (cy.done || panicked) {
     if (gtid == 0) {
@@ -109,7 +103,7 @@ __global__ __launch_bounds__(kPThreads) void sssp_part_kernel(SsspArgs a) {
       // an idle launch still sends a well-formed, empty outbox
       publish(&a.outbox[0], 0u); publish(&a.outbox[1], 1u); publish(&a.outbox[2], 0u); publish(&a.outbox[3], 0u);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      report(cy, panicked);
+      part_report(a.mail, k, cy, panicked);
     }
     return;
   }
@@ -367,7 +361,7 @@ __global__ __launch_bounds__(kPThreads) void sssp_part_kernel(SsspArgs a) {
     st->carry[(k + 1) & 1] = cy;
     if (cy.done) *a.result = cy;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    report(cy, false);
+    part_report(a.mail, k, cy, false);
   }
 }
 
@@ -393,20 +387,6 @@ __global__ void sssp_part_copy_kernel(const unsigned int* __restrict__ D_own, fl
   if (i < n_local) out[i] = __uint_as_float(D_own[i]);
 }
 
-constexpr int kLoopMaxRanksS = 16;
-struct LoopbackPtrsS {
-  const unsigned int* send[kLoopMaxRanksS];
-  unsigned int* recv[kLoopMaxRanksS];
-};
-__global__ __launch_bounds__(kBlock) void sssp_loopback_allgather_kernel(LoopbackPtrsS p, int world, int nwords) {
-  const long long total = (long long)world * nwords;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < total; i += (long long)gridDim.x * kBlock) {
-    const int r = (int)(i / nwords);
-    const unsigned int x = p.send[r][i - (long long)r * nwords];
-    for (int q = 0; q < world; ++q) p.recv[q][i] = x;
-  }
-}
-
 }  // namespace grb
 
 using namespace grb;
@@ -421,18 +401,10 @@ struct grb_part_sssp_s {
   unsigned int *D = nullptr, *dcur = nullptr, *outbox = nullptr, *inboxes = nullptr;
   Index* Q[2] = {nullptr, nullptr};
   int2* C[2] = {nullptr, nullptr};
-  unsigned long long *h_mail = nullptr, *d_mail = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  PartMail mail;
 };
 
 namespace {
-
-void sssp_mail_peek(grb_part_sssp p, int* launches_done, int* done_at) {
-  const unsigned long long g = __atomic_load_n(p->h_mail, __ATOMIC_ACQUIRE);
-  *launches_done = (int)(g & 0xffffffffull);
-  const unsigned int hi = (unsigned int)(g >> 32);
-  *done_at = hi == 0xffffffffu ? -2 : (int)hi - 1;
-}
 
 grb_info part_sssp_run(grb_part_sssp* ps, int nranks, grb_index source, int max_niter, int rounds_per_launch,
                        float* const* d_dist_local, grb_part_sssp_result* res) {
@@ -441,25 +413,17 @@ grb_info part_sssp_run(grb_part_sssp* ps, int nranks, grb_index source, int max_
   grb_part_sssp p0 = ps[0];
   const bool loopback = nranks > 1;
   const int world = p0->world;
-  if (loopback && (world != nranks || nranks > kLoopMaxRanksS)) return GRB_INVALID_VALUE;
+  if (loopback && (world != nranks || nranks > kLoopMaxRanks)) return GRB_INVALID_VALUE;
   if (source < 0 || source >= p0->n) return GRB_INVALID_INDEX;
   if (max_niter < 1) return GRB_INVALID_VALUE;
-  if (!loopback && world > 1) {
-    int r = -1, w = 0;
-    grb_comm_info(&r, &w);
-    if (w != world || r != p0->rank) return GRB_UNINITIALIZED_OBJECT;
-  }
+  if (!loopback && world > 1 && !part_comm_matches(p0->rank, world)) return GRB_UNINITIALIZED_OBJECT;
   if (world > 1 || rounds_per_launch < 1) rounds_per_launch = 1;
   GRB_TRY(bfs_lanes_fence(ctx().stream));   // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, sssp_part_kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
-  }
+  GRB_TRY(persistent_kernel_fits<sssp_part_kernel>());
   const int G = c.num_cu;
   const int words = kSsspHdr + 2 * p0->cap;
   std::vector<SsspArgs> args(nranks);
-  LoopbackPtrsS lp = {};
+  LoopbackPtrs lp = {};
   for (int r = 0; r < nranks; ++r) {
     grb_part_sssp p = ps[r];
     if (p->cap != p0->cap) return GRB_INVALID_VALUE;
@@ -476,11 +440,11 @@ grb_info part_sssp_run(grb_part_sssp* ps, int nranks, grb_index source, int max_
     a.inboxes = world > 1 ? p->inboxes : p->outbox;
     a.cap = p->cap;
     a.st = (SsspState*)p->d_block;
-    a.mail = p->d_mail;
-    a.result = reinterpret_cast<SsspCarry*>(p->d_mail + 8);
+    a.mail = p->mail.d_mail;
+    a.result = p->mail.d_carry<SsspCarry>();
     a.launch = 0;
     a.nsteps = rounds_per_launch;
-    __atomic_store_n(p->h_mail, 0ull, __ATOMIC_RELEASE);
+    p->mail.reset();
     GRB_HIP_TRY(hipMemsetAsync(p->d_block, 0, p->st_bytes, s));
     GRB_HIP_TRY(hipMemsetAsync(p->outbox, 0, 4 * (size_t)kSsspHdr, s));
     hipLaunchKernelGGL(sssp_part_init_kernel, dim3(stream_grid(p->n)), dim3(kBlock), 0, s, p->D, p->n, p->dcur, p->lo,
@@ -488,42 +452,22 @@ grb_info part_sssp_run(grb_part_sssp* ps, int nranks, grb_index source, int max_
     GRB_HIP_TRY(hipGetLastError());
     if (loopback) { lp.send[r] = p->outbox; lp.recv[r] = p->inboxes; }
   }
-  const auto t0 = std::chrono::steady_clock::now();
-  GRB_HIP_TRY(hipEventRecord(p0->ev0, s));
   int k = 0;
-  for (;;) {
-    if (k >= 2) {                                        // the launch rule of grb_bfs_part_run
-      unsigned spins = 0;
-      bool synced = false;
-      int ld = 0, done_at = -1;
-      for (;;) {
-        sssp_mail_peek(p0, &ld, &done_at);
-        if (ld >= k - 1) break;
-        if ((++spins & 4095u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-          if (synced) return GRB_PANIC;
-          GRB_HIP_TRY(hipStreamSynchronize(s));
-          synced = true;
-        }
-      }
-      if (done_at == -2) return GRB_PANIC;
-      if (done_at >= 0 && done_at <= k - 2) break;
-    }
+  auto enqueue = [&](int launch) -> grb_info {         // launch `launch` of every rank, and its exchange
     for (int r = 0; r < nranks; ++r) {
-      args[r].launch = k;
+      args[r].launch = launch;
       hipLaunchKernelGGL(sssp_part_kernel, dim3(G), dim3(kPThreads), 0, s, args[r]);
       GRB_HIP_TRY(hipGetLastError());
     }
     if (loopback) {
-      hipLaunchKernelGGL(sssp_loopback_allgather_kernel, dim3(stream_grid((long long)nranks * words)), dim3(kBlock), 0, s, lp,
-                         nranks, words);
-      GRB_HIP_TRY(hipGetLastError());
+      GRB_TRY(loopback_allgather(lp, nranks, words, s));
     } else if (world > 1) {
       GRB_TRY(grb_comm_allgather(p0->outbox, p0->inboxes, 4 * (size_t)words));
       GRB_TRY(grb_comm_wait());
     }
-    ++k;
-    if (k > (1 << 28)) return GRB_PANIC;
-  }
+    return GRB_SUCCESS;
+  };
+  GRB_TRY(p0->mail.drive(s, enqueue, 60, false, &k));
   for (int r = 0; r < nranks; ++r) {
     grb_part_sssp p = ps[r];
     if (p->n_local > 0 && d_dist_local[r]) {
@@ -532,17 +476,12 @@ grb_info part_sssp_run(grb_part_sssp* ps, int nranks, grb_index source, int max_
       GRB_HIP_TRY(hipGetLastError());
     }
   }
-  GRB_HIP_TRY(hipEventRecord(p0->ev1, s));
-  GRB_HIP_TRY(hipEventSynchronize(p0->ev1));
   float ms = 0.f;
-  GRB_HIP_TRY(hipEventElapsedTime(&ms, p0->ev0, p0->ev1));
+  GRB_TRY(p0->mail.elapsed_ms(s, &ms));
   for (int r = 0; r < nranks; ++r) {
     grb_part_sssp p = ps[r];
-    int ld = 0, done_at = -1;
-    sssp_mail_peek(p, &ld, &done_at);
     SsspCarry cy;
-    memcpy(&cy, p->h_mail + 8, sizeof(cy));
-    if (done_at < 0 || !cy.done) return GRB_PANIC;
+    GRB_TRY(p->mail.read_carry(&cy));
     if (res) {
       res[r].iterations = cy.iterations;
       res[r].rounds = cy.round;
@@ -588,11 +527,7 @@ grb_info grb_part_sssp_new(grb_part_sssp* out, int rank, int world, grb_index n_
   p->C[1] = (int2*)q; q += 8 * (size_t)p->ccap;
   p->outbox = (unsigned int*)q;
   if (world > 1 && hipMalloc((void**)&p->inboxes, 4 * words * (size_t)world) != hipSuccess) return fail(GRB_OUT_OF_MEMORY);
-  if (hipHostMalloc((void**)&p->h_mail, 256, hipHostMallocMapped) != hipSuccess) return fail(GRB_OUT_OF_MEMORY);
-  memset(p->h_mail, 0, 256);
-  static_assert(sizeof(SsspCarry) <= 256 - 64, "the result record follows the mail word in pinned memory");
-  if (hipHostGetDevicePointer((void**)&p->d_mail, p->h_mail, 0) != hipSuccess) return fail(GRB_PANIC);
-  if (hipEventCreate(&p->ev0) != hipSuccess || hipEventCreate(&p->ev1) != hipSuccess) return fail(GRB_PANIC);
+  if (const grb_info mi = p->mail.create()) return fail(mi);
   *out = p;
   return GRB_SUCCESS;
 }
@@ -602,9 +537,7 @@ grb_info grb_part_sssp_free(grb_part_sssp p) { GRB_API_ENTER();
   (void)hipStreamSynchronize(ctx().stream);
   if (p->d_block) (void)hipFree(p->d_block);
   if (p->inboxes) (void)hipFree(p->inboxes);
-  if (p->h_mail) (void)hipHostFree(p->h_mail);
-  if (p->ev0) (void)hipEventDestroy(p->ev0);
-  if (p->ev1) (void)hipEventDestroy(p->ev1);
+  p->mail.destroy();
   delete p;
   return GRB_SUCCESS;
 }

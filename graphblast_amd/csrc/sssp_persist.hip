@@ -306,13 +306,11 @@ incl = (int)wave_incl_scan_u32((unsigned)incl);
     }
   }
   if (gtid == 0) {
-    const unsigned long long tag = (unsigned long long)(unsigned int)a.seq << 32;
+    const unsigned int seq = (unsigned int)a.seq;          // read in front of the clock, where the tag was made
     const float ms = (float)(wall_clock64() - t_start) * a.ticks_to_ms;
     const unsigned int vals[4] = {(unsigned int)(iter > a.max_niter ? a.max_niter + 1 : iter), (unsigned int)succ,
                                   __float_as_uint(ms), (unsigned int)bailed};
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      __hip_atomic_store(&a.mail[k], tag | vals[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    mail_granules(a.mail, seq, vals);
   }
 }
 
@@ -364,11 +362,7 @@ grb_info sssp_persistent_run(grb_vector v, grb_matrix A, grb_index source, grb_d
 
   const int nwords = 2 * ceil_div(n, 64);
   GRB_TRY(bfs_lanes_fence(ctx().stream));   // a whole-device grid must not meet a BFS lane's narrower one half-way (bfs_persist.hip)
-  static int max_per_cu = 0;
-  if (!max_per_cu) {
-    GRB_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&max_per_cu, sssp_persistent_kernel, kPThreads, 0));
-    if (max_per_cu < 1) return GRB_PANIC;
-  }
+  GRB_TRY(persistent_kernel_fits<sssp_persistent_kernel>());
   const int G = c.num_cu;
   const int big_cap = (int)(A->nvals / kSsspBig) + 2;
   const size_t st_bytes = (sizeof(SsspState) + 255) & ~(size_t)255;
@@ -378,13 +372,6 @@ grb_info sssp_persistent_run(grb_vector v, grb_matrix A, grb_index source, grb_d
   ctx().bfs_prezero_ptr = nullptr;          // this slot is about to be overwritten
   GRB_TRY(scratch(8, 8 * (size_t)n + 8, &p_c));
   GRB_TRY(scratch(2, sizeof(int2) * (size_t)big_cap, &p_big));
-  static float ticks_to_ms = 0.f;
-  if (ticks_to_ms == 0.f) {
-    int khz = 0, dev = 0;
-    GRB_HIP_TRY(hipGetDevice(&dev));
-    GRB_HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-    ticks_to_ms = khz > 0 ? 1.0f / (float)khz : 1e-5f;
-  }
   SsspArgs a;
   a.optr = A->csr.ptr; a.oind = A->csr.ind; a.oval = (const float*)A->csr.val;
   a.n = n;
@@ -404,7 +391,7 @@ grb_info sssp_persistent_run(grb_vector v, grb_matrix A, grb_index source, grb_d
   a.st = (SsspState*)p_zero;
   a.mail = c.d_hgran;
   a.seq = ++c.mail_seq;
-  a.ticks_to_ms = ticks_to_ms;
+  GRB_TRY(wall_ticks_to_ms(&a.ticks_to_ms));
   const int rec_cap = 1 << 16;
   a.rec = nullptr;
   a.rec_cap = 0;

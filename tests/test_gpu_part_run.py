@@ -219,6 +219,11 @@ def test_device_loop_sssp_directed_and_road_like():
         d, info = part.sssp(w, 0, rounds_per_launch=rpl)
         assert np.array_equal(d.cpu().numpy(), want_d) and info["iterations"] == want_it, (rpl, info, want_it)
         assert info["form"].startswith("frontier")
+    # the launch rule (csrc/part_driver.hpp): launch 0 runs every round, one spare launch follows it
+    part = Partition1D(gr["n"], _t(ptr, dev), _t(ind, dev), 0, 1, dev)
+    d, info = part.sssp(w, 0, rounds_per_launch=1 << 20)
+    assert np.array_equal(d.cpu().numpy(), want_d) and info["iterations"] == want_it
+    assert info["launches"] == 2, info
     for world in (3,):
         grp = LoopbackGroup(gr["n"], _t(ptr, dev), _t(ind, dev), world, dev)
         d, res = grp.sssp(w, 0, outbox_pairs=64)
