@@ -31,6 +31,7 @@
 #include "bfs_kernels.hpp"
 #include "persist_common.hpp"
 #include "batch_decide.hpp"
+#include "batch_slots.hpp"
 #include <chrono>
 #include <climits>
 
@@ -46,6 +47,7 @@ constexpr int kBatchStoreMax = 16;    // level words kept for the final label pa
 constexpr int kBatchCounters = 2 + 128 + 2;   // per slot: vertices, the big in-rows still open (below), {nf_s, mf_s} per source, big out-rows found, U (below)
 constexpr int kCntInOpen = 1, kCntBigOut = 2 + 128, kCntOpenU = 2 + 128 + 1;
 static_assert(kBatchCounters <= kBlock, "batch_totals_kernel sums a counter per thread");
+static_assert(kBatchStoreMax + 1 == kSlotsKeptMax, "batch_slots.hpp records a level per kept slot");
 constexpr int kBatchBoxPer = kBatchCounters + 9;      // the host's box: where the light-level launch leaves TailState::cum and ::last
 constexpr int kBoxDecision = kBatchCounters + 5;      // box: {qmask, pmask, kind, stash} of the NEXT level, as batch_totals_kernel decided it
 constexpr int kBatchCtlWords = 5;                     // the device's copy of the first three, behind the counter slots; [3]: the last light-level launch's status; [4]: stash
@@ -1517,19 +1519,42 @@ extern "C" long long grb_bfs_batch_set_tail(long long edges) { GRB_API_ENTER_NOI
 // once (bfs_sweep_provision) -- slot 7 is the one-launch traversal's pre-zeroed block, and a blocking call after a routed
 // sweep must not find it taken.
 namespace {
+// The rotating word arrays a complete sweep left all-zero, and the sizes it ran at (the light-level launch leaves its
+// arrays so).  take() hands the knowledge to the sweep that starts and voids the record: a sweep that fails in between
+// leaves none.
+struct SweepClean {
+  bool valid = false, clean[4] = {false, false, false, false};
+  Index n = 0;
+  size_t stride = 0;
+  int nstore = 0;
+  void take(bool mine, Index n_, size_t stride_, int nstore_, bool* out) {
+    const bool ok = mine && valid && n == n_ && stride == stride_ && nstore == nstore_;
+    for (int i = 0; i < 4; ++i) out[i] = ok && clean[i];
+    valid = false;
+  }
+  void keep(Index n_, size_t stride_, int nstore_, const bool* now) {
+    valid = true; n = n_; stride = stride_; nstore = nstore_;
+    for (int i = 0; i < 4; ++i) clean[i] = now[i];
+  }
+};
 struct SweepOwn {
   void *words = nullptr, *cnt = nullptr, *tail = nullptr, *list = nullptr;
   size_t words_cap = 0, tail_cap = 0, list_cap = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool clean_valid = false, clean[4] = {false, false, false, false};   // the rotating arrays known all-zero, for (clean_n, clean_nstore)
-  Index clean_n = 0;
-  size_t clean_stride = 0;
-  int clean_nstore = 0;
+  SweepClean zero;                                          // (nobody else ever has these buffers)
   bool small_clean = false;                                 // the counter slots and the big-row list's length are zero, as every complete sweep leaves them
   bool warmed = false;                                      // every batch_* kernel has been launched once ...
   bool warmed_own_small = false, warmed_own_wide = false;   // ... the two owner-computes instances too (they need a matrix with ranges)
 };
 SweepOwn g_sweep;
+// the scratch-slot route's events and its record, which holds only while nobody else has had slot 7 in between
+struct SweepScratch {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  SweepClean zero;
+  unsigned long long epoch = 0;
+  void* ptr = nullptr;
+};
+SweepScratch g_sweep_scratch;
 struct SweepSizes {
   int nstore = 1;
   size_t stride = 0;                                        // words from one array to the next: n, or n + H rounded up to 256 bytes
@@ -1574,166 +1599,34 @@ static grb_info batch_box() {
   return GRB_SUCCESS;
 }
 
-// k traversals of A (both orientations, the pull hint and the slice tables ready) from sources[] into v[] under the rules
-// (mode, max_niter, switchpoint).  per != nullptr: every source's own result block, as its own one-launch traversal
-// would report it -- reached = 1 + its discoveries, edges = its out-degree + theirs, levels = the iterations its own loop
-// runs (up to and including the first that discovers nothing, at most max_niter), tight_ms = the sweep's device time / k;
-// per_dir[s] = 1 when the source's last productive level was pulled.  Timed with HIP events of its own (the library's
-// timer belongs to the caller); returns after the label pass has completed.
-static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index* sources, int rules_mode, int max_niter,
-                            float switchpoint, SweepOwn* own, grb_bfs_result* per, int* per_dir, SweepTotals* out) {
-  Context& c = ctx();
-  hipStream_t st = c.stream;
-  const Index n = A->nrows;
-  SweepSizes z = sweep_sizes(A);
-  void *p_words, *p_cnt;
-  static hipEvent_t s_ev0 = nullptr, s_ev1 = nullptr;
-  hipEvent_t ev0, ev1;
-  if (own) {
-    if (!own->words || own->words_cap < z.words || own->tail_cap < z.tail || own->list_cap < z.list || !own->ev0) return GRB_OUT_OF_MEMORY;
-    p_words = own->words; p_cnt = own->cnt;
-    ev0 = own->ev0; ev1 = own->ev1;
-  } else {
-    grb_info wi = scratch(7, z.words, &p_words);
-    if (wi != GRB_SUCCESS && A->batch_hot.H > 0) {          // no room for the tails: the sweep runs without the hot block
-      (void)hipGetLastError();
-      hot_drop(A);
-      z = sweep_sizes(A);
-      wi = scratch(7, z.words, &p_words);
-    }
-    GRB_TRY(wi);
-    c.bfs_prezero_ptr = nullptr;                            // slot 7 is the one-launch traversal's pre-zeroed block
-    GRB_TRY(scratch(10, sizeof(u64) * (kBatchSlots * kBatchCounters + kBatchCtlWords), &p_cnt));
-    if (!s_ev0) {
-      GRB_HIP_TRY(hipEventCreate(&s_ev0));
-      GRB_HIP_TRY(hipEventCreate(&s_ev1));
-    }
-    ev0 = s_ev0; ev1 = s_ev1;
-  }
-  const int nstore = z.nstore;
-  const size_t stride = z.stride;
-  // the hot block: H hub words behind the n of every level-word array; the pull kernels' own copies of the CSC indices and
-  // of the hint name hub j as n + j (H = 0: the matrix's arrays as they are)
-  const BatchHot& hot = A->batch_hot;
-  const Index H = hot.H;
-  u64* seen = (u64*)p_words;
-  // level words: slot 0 .. nstore are kept for the label pass (which level each holds is recorded as it is taken; slot 0
-  // the seeds, or level 1 when the first level is the plain launch);
-  // four more rotate -- a level beyond the kept ones (it labels as it discovers) and the three word arrays of the
-  // light-level launch
-  auto Slot = [&](int i) -> u64* { return seen + (size_t)(1 + i) * stride; };
-  u64* const pool[4] = {Slot(nstore + 1), Slot(nstore + 2), Slot(nstore + 3), Slot(nstore + 4)};
-  // known all-zero: the light-level launch leaves its arrays so, and the knowledge survives to the next sweep if nobody
-  // else has had the scratch slot in between
-  static struct { bool valid = false; unsigned long long epoch = 0; void* ptr = nullptr; Index n = 0; size_t stride = 0; int nstore = 0; bool clean[4]; } kept_pool;
-  bool pool_clean[4] = {false, false, false, false};
-  if (own) {                                                // (nobody else ever has these buffers)
-    if (own->clean_valid && own->clean_n == n && own->clean_stride == stride && own->clean_nstore == nstore)
-      for (int i = 0; i < 4; ++i) pool_clean[i] = own->clean[i];
-    own->clean_valid = false;
-  } else {
-    if (kept_pool.valid && kept_pool.epoch + 1 == c.slot_epoch[7] && kept_pool.ptr == p_words && kept_pool.n == n && kept_pool.stride == stride && kept_pool.nstore == nstore)
-      for (int i = 0; i < 4; ++i) pool_clean[i] = kept_pool.clean[i];
-    kept_pool.valid = false;
-  }
-  // a rotating array other than x and y: for the light-level launch a clean one if there is one (no memset), for
-  // everybody else a dirty one (so that the clean ones stay clean)
-  auto pick = [&](const u64* x, const u64* y, const u64* z, bool want_clean) -> int {
-    int other = -1;
-    for (int i = 0; i < 4; ++i) {
-      if (pool[i] == x || pool[i] == y || pool[i] == z) continue;
-      if (pool_clean[i] == want_clean) return i;
-      if (other < 0) other = i;
-    }
-    return other;
-  };
-  const u64* kept_words[kBatchStoreMax + 1];
-  int kept_level[kBatchStoreMax + 1];
-  int nkept = 1;                                            // the seeds (taken back below when the first level needs no seed words)
-  kept_words[0] = Slot(0);
-  kept_level[0] = 0;
-  bool any_direct = false;
-  const u64* fcur_words = Slot(0);
-  BatchArgs a;
-  a.optr = A->csr.ptr; a.oind = A->csr.ind; a.iptr = A->csc.ptr; a.iind = A->csc.ind;
-  a.hint = A->d_pull_hint;
-  a.n = n;
-  a.seen = seen;
-  a.counters = (u64*)p_cnt;
-  a.k = k;
-  a.ctl = nullptr;
-  a.list_len = nullptr;
-  a.claims = 0; a.stash = 0;
-  a.big_index = nullptr; a.list = nullptr; a.list_fw = nullptr;
-  a.big_out = batch_big(false);
-  u64* const d_ctl = a.counters + kBatchSlots * kBatchCounters;   // written by every totals kernel before anybody reads it
-  for (int s = 0; s < 64; ++s) a.label[s] = nullptr;
-  for (int s = 0; s < k; ++s) {
-    GRB_TRY(grb_vector_set_storage(v[s], GRB_DENSE));
-    a.label[s] = (float*)v[s]->d_val;
-  }
-  GRB_TRY(batch_box());
-  u64 *const h_box = g_box_h, *const d_box = g_box_d;
-  u64& box_seq = g_box_seq;
-  // The counter slots are left zero by every totals kernel and the big-row list's length by the commit kernel behind the
-  // owner kernels, so a sweep that ran to its end leaves both zero; on the sweep's own buffers, which nobody else has, that
-  // is remembered, and a sweep that fails in between clears them at the next start.
-  void* p_list = own ? own->list : nullptr;
-  if (!own) GRB_TRY(scratch(11, z.list, &p_list));
-  unsigned int* const d_count = (unsigned int*)p_list;
-  if (!(own && own->small_clean)) {
-    GRB_HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
-    GRB_HIP_TRY(hipMemsetAsync(d_count, 0, kListHeader, st));
-  }
-  if (own) own->small_clean = false;
-  // the light-level launches' state blocks, all of them now: the fill runs while the host is still enqueuing the sweep's
-  // start, not between a level's totals and the launch that waits for it
-  void* p_tail = own ? own->tail : nullptr;
-  int tail_states_used = 0;
-  if (batch_tail_limit() > 0) {
-    if (!own) GRB_TRY(scratch(8, z.tail, &p_tail));
-    GRB_HIP_TRY(hipMemsetAsync(p_tail, 0, kTailStates * z.tail_state, st));
-  }
-  GRB_HIP_TRY(hipMemsetAsync(seen, 0, sizeof(u64) * (stride + (size_t)n), st));   // seen and the seeds' words (and seen's unused tail)
-  SeedSources seeds;
-  for (int s = 0; s < 64; ++s) seeds.v[s] = s < k ? (Index)sources[s] : 0;
+// ---- layouts and launch sites the sweep shares with sweep_warm ---------------------------------------------------------
+namespace {
+struct ListBlock {                                          // the big-row list of an owner-computes level
+  unsigned int* len;                                        // kListSegs lengths, kListLenStride apart
+  int* ids;
+  u64* words;
+};
+}  // namespace
+static ListBlock list_carve(void* p_list, const SweepSizes& z) {
+  return {(unsigned int*)p_list, (int*)((char*)p_list + kListHeader), (u64*)((char*)p_list + kListHeader + z.list_ids)};
+}
+// the light-level launch's state block `state` of the kTailStates and its three queues behind them
+static void tail_carve(TailArgs& t, void* p_tail, const SweepSizes& z, int state) {
+  t.st = (TailState*)((char*)p_tail + (size_t)state * z.tail_state);
+  for (int i = 0; i < 3; ++i) t.queue[i] = (u64*)((char*)p_tail + kTailStates * z.tail_state) + (size_t)i * z.qcap;
+}
+// the owners of `count` destination ranges, taken from range_ids[first] on
+template <int Rows, int Threads>
+static void launch_owners(const BatchArgs& a, const BatchSlices& B, const ListBlock& L, int first, int count, hipStream_t st) {
+  hipLaunchKernelGGL((batch_push_owner_kernel<Rows, Threads>), dim3(count), dim3(Threads), 0, st, a, (const Index*)B.d_range_off,
+                     (int)own_off_stride(B.nranges), (const int*)L.ids, (const u64*)L.words, (const unsigned int*)L.len,
+                     (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + first);
+}
 
-  // per-source frontier totals of the seed level
-  unsigned long long nf_s[64], mf_s[64];
-  unsigned long long edges = 0, reached = (unsigned long long)k;
-  unsigned long long reached_s[64], edges_s[64];            // per source, for `per`
-  int last_prod[64], dir_s[64];                             // the last iteration at which the source discovered anything; its direction
-  for (int s = 0; s < k; ++s) {
-    nf_s[s] = 1;
-    mf_s[s] = (unsigned long long)(A->h_csr_ptr[(size_t)sources[s] + 1] - A->h_csr_ptr[sources[s]]);
-    edges += mf_s[s];
-    reached_s[s] = 1; edges_s[s] = mf_s[s]; last_prod[s] = 0; dir_s[s] = 0;
-  }
-  // GRB_SPARSE_MATRIX_FORMAT = 1: no CSC storage -- the "CSC" arrays ARE the CSR arrays, and the reference's vxm
-  // is forced to push whatever the mxvmode says (operations.hpp:131-133).  A pull over them would walk out-edges
-  // as if they were in-edges: every source is pushed.
-  const int mode = (A->format != 0 || A->csc_alias) ? GRB_PUSHONLY : rules_mode;
-  const int grid = stream_grid((long long)ceil_div(n, kWave) * kWave, kBlock);
-  int iter = 1, levels = 0, last_dir = 0;
-  bool any_left = true;
-  float ms = 0.f;
-  static const bool trace = getenv("GRB_BATCH_TRACE") != nullptr;
-  static const double budget = getenv("GRB_BATCH_BUDGET") ? atof(getenv("GRB_BATCH_BUDGET")) : 0.15;
-  const double tail_edges = (double)batch_tail_limit();
-  const bool tail_on = tail_edges > 0;
-  auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  // results come back through the pinned, host-coherent box the host polls: no copy, no stream wait
-  auto wait_box = [&]() -> grb_info {
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(&h_box[kBatchCounters], __ATOMIC_ACQUIRE) != box_seq) {
-      if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
-        GRB_HIP_TRY(hipStreamSynchronize(st));               // a long level, or a fault this wait reports
-        if (__atomic_load_n(&h_box[kBatchCounters], __ATOMIC_ACQUIRE) != box_seq) return GRB_PANIC;
-      }
-    }
-    return GRB_SUCCESS;
-  };
+// ---- the knobs, read at the first sweep of the process ------------------------------------------------------------------
+namespace {
+struct SweepKnobs {
+  bool trace;                                               // GRB_BATCH_TRACE: a line per level on stderr
   // ---- direction per source: the reference's vertex-count rule (switchpoint) on that source's own frontier, and a
   // budget on the edges pushed in one level (batch_decide.hpp): pull the sources whose own frontier passed the
   // reference's switch point (their bits are found within a few probes, so the early exit works); push the others --
@@ -1741,6 +1634,7 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   // plus an atomic on it, about 50 G edges/s on RMAT-22 against 85 G/s for a pulled entry), then the heaviest of them
   // are pulled as well.  The host decides the sweep's first level and the one after a light-level launch; after a level
   // of this loop the totals kernel has decided the next one on the device, and that decision is the one used.
+  double budget;
   // ---- the finishing rule.  At a sweep's end a source is under the switch point because almost nothing is left for it to
   // find, and pushing it costs what a push stage costs whatever it pushes: batch_push_kernel reads all n frontier words to
   // find the few that carry a pushed bit, batch_push_commit_kernel reads all n words again to count what arrived (26 us a
@@ -1751,49 +1645,152 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
   // sources are pulled too and the level has no push stage (batch_decide_finish).  Only the totals kernel ever has a
   // complete U: the levels the host decides (the first, the one after a light-level launch) keep the per-source rule, as
   // does a level after one that pushed anything or a level that pulls nobody.  GRB_BATCH_FINISH=0: no such rule.
-  static const double finish_limit = [] {
-    const char* on = getenv("GRB_BATCH_FINISH");
-    if (on && atoi(on) == 0) return -1.0;
-    const char* e = getenv("GRB_BATCH_FINISH_LIMIT");
-    return e ? atof(e) : 0.01;
-  }();
-  BatchRule rule;
-  rule.k = k; rule.n = (long long)n; rule.nvals = (long long)A->nvals;
-  rule.mode = mode == GRB_PULLONLY ? kDecidePullOnly : mode == GRB_PUSHONLY ? kDecidePushOnly : kDecidePushPull;
-  rule.switchpoint = switchpoint; rule.budget = budget; rule.tail_limit = tail_on ? tail_edges : 0.0;
-  rule.finish_limit = finish_limit;
+  double finish_limit;
   // Launching ahead: behind a level's totals kernel the NEXT level's pull kernels are enqueued at once, before the host
   // has the totals -- they take their bits from the control block the totals kernel leaves, and return at once when that
   // level is no level of this loop.  The GPU then pulls while the host turns the level round.  Stream order is all this
   // relies on.  GRB_BATCH_AHEAD=0: wait, then launch (for A/B runs in fresh processes).
-  static const bool ahead_on = [] { const char* e = getenv("GRB_BATCH_AHEAD"); return !e || atoi(e) != 0; }();
-  const bool ahead = ahead_on && mode != GRB_PUSHONLY;
-  // where a level's words go is a PLAN until the level is known to be one of this loop: a kept slot while there are any
-  // (the label pass reads it), else a rotating array that labels as it discovers
-  struct Plan { bool keep; int fi; u64* fnext; };
-  auto plan_slot = [&](const u64* fcur) {
-    Plan p;
-    p.keep = nkept <= nstore;
-    p.fi = p.keep ? -1 : pick(fcur, nullptr, nullptr, false);
-    p.fnext = p.keep ? Slot(nkept) : pool[p.fi];
-    return p;
-  };
-  auto commit_slot = [&](const Plan& p, int it) {
-    if (p.fi >= 0) pool_clean[p.fi] = false;
-    if (p.keep) { kept_words[nkept] = p.fnext; kept_level[nkept] = it; ++nkept; } else any_direct = true;
-  };
+  bool ahead;
+  bool owner;                                               // GRB_BATCH_OWNER=0: no owner-computes push, the slice kernel takes the big rows
+  bool owner_merge;                                         // GRB_BATCH_OWNER_MERGE=0: always the two owner launches (push_stage)
+};
+}  // namespace
+static const SweepKnobs& sweep_knobs() {
+  static const SweepKnobs knobs = [] {
+    auto on = [](const char* name) { const char* e = getenv(name); return !e || atoi(e) != 0; };
+    SweepKnobs x;
+    x.trace = getenv("GRB_BATCH_TRACE") != nullptr;
+    x.budget = getenv("GRB_BATCH_BUDGET") ? atof(getenv("GRB_BATCH_BUDGET")) : 0.15;
+    const char* limit = getenv("GRB_BATCH_FINISH_LIMIT");
+    x.finish_limit = !on("GRB_BATCH_FINISH") ? -1.0 : limit ? atof(limit) : 0.01;
+    x.ahead = on("GRB_BATCH_AHEAD");
+    x.owner = on("GRB_BATCH_OWNER");
+    x.owner_merge = on("GRB_BATCH_OWNER_MERGE");
+    return x;
+  }();
+  return knobs;
+}
+
+// ---- where the sweep's four buffers, two events and its record of zero arrays come from ---------------------------------
+namespace {
+struct SweepBufs {
+  void *words = nullptr, *cnt = nullptr, *tail = nullptr, *list = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  SweepClean* zero = nullptr;
+  bool zero_mine = false;                                   // nobody else has had the words since the record was made
+};
+}  // namespace
+// own: the provisioned buffers.  Else scratch slots 7, 10, 11 and (with_tail) 8 -- and when slot 7 has no room for the
+// hubs' tails the matrix loses its hot block and z is taken again.
+static grb_info sweep_resolve(grb_matrix A, SweepOwn* own, bool with_tail, SweepSizes& z, SweepBufs& b) {
+  if (own) {
+    if (!own->words || own->words_cap < z.words || own->tail_cap < z.tail || own->list_cap < z.list || !own->ev0) return GRB_OUT_OF_MEMORY;
+    b.words = own->words; b.cnt = own->cnt; b.tail = own->tail; b.list = own->list;
+    b.ev0 = own->ev0; b.ev1 = own->ev1;
+    b.zero = &own->zero;
+    b.zero_mine = true;
+    return GRB_SUCCESS;
+  }
+  Context& c = ctx();
+  SweepScratch& s = g_sweep_scratch;
+  grb_info wi = scratch(7, z.words, &b.words);
+  if (wi != GRB_SUCCESS && A->batch_hot.H > 0) {            // no room for the tails: the sweep runs without the hot block
+    (void)hipGetLastError();
+    hot_drop(A);
+    z = sweep_sizes(A);
+    wi = scratch(7, z.words, &b.words);
+  }
+  GRB_TRY(wi);
+  c.bfs_prezero_ptr = nullptr;                              // slot 7 is the one-launch traversal's pre-zeroed block
+  GRB_TRY(scratch(10, sizeof(u64) * (kBatchSlots * kBatchCounters + kBatchCtlWords), &b.cnt));
+  GRB_TRY(scratch(11, z.list, &b.list));
+  if (with_tail) GRB_TRY(scratch(8, z.tail, &b.tail));
+  if (!s.ev0) {
+    GRB_HIP_TRY(hipEventCreate(&s.ev0));
+    GRB_HIP_TRY(hipEventCreate(&s.ev1));
+  }
+  b.ev0 = s.ev0; b.ev1 = s.ev1;
+  b.zero = &s.zero;
+  b.zero_mine = s.epoch + 1 == c.slot_epoch[7] && s.ptr == b.words;
+  return GRB_SUCCESS;
+}
+
+// ---- one sweep: what its stages share, and the stages in the order batch_sweep runs them --------------------------------
+namespace {
+double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct Sweep {
+  // the call
+  const int k;
+  const grb_matrix A;
+  const int max_niter;
+  SweepOwn* const own;
+  grb_bfs_result* const per;
+  // fixed from begin() on
+  const SweepKnobs& knobs = sweep_knobs();
+  Context& c = ctx();
+  const hipStream_t st = c.stream;
+  const Index n = A->nrows;
+  SweepSizes z = sweep_sizes(A);
+  SweepBufs buf;
+  ListBlock list;
+  Index H = 0, Hcopy = 0;                                   // the hot block's hubs; those a totals launch copies (0 when nobody pulls: no tail is ever read)
+  u64 *seen = nullptr, *d_ctl = nullptr;
+  int grid = 0;
+  double tail_edges = 0;
+  bool ahead = false, first_plain = false;
+  SeedSources seeds;
+  BatchRule rule;
+  BatchArgs a;
+  BatchSlots slots;
+  // the traversals so far
+  unsigned long long nf_s[64], mf_s[64];                    // per-source frontier totals of the last level
+  unsigned long long edges = 0, reached = 0;
+  unsigned long long reached_s[64], edges_s[64];            // per source, for `per`
+  int last_prod[64], dir_s[64];                             // the last iteration at which the source discovered anything; its direction
+  int iter = 1, levels = 0, last_dir = 0;
+  bool any_left = true;
   bool in_done = false;                                     // every big in-row has every source's bit: nothing left for the slice kernels
-  // the tail of fcur_words holds the hubs' words as they stand: a totals launch has copied them.  Not so for the seeds'
-  // words, nor for the array a light-level launch hands back: a pull of those is preceded by a copy launch of its own
+  // the tail of the frontier's array holds the hubs' words as they stand: a totals launch has copied them.  Not so for the
+  // seeds' words, nor for the array a light-level launch hands back: a pull of those is preceded by a copy launch of its own
   bool tail_fresh = false;
-  const Index Hcopy = mode == GRB_PUSHONLY ? 0 : H;         // (nobody pulls: no tail is ever read)
   long long big_out_new = -1;                               // big out-rows among the frontier's vertices (-1: not counted, the light-level launch's hand-back)
-  auto launch_pull = [&](BatchArgs& x) -> grb_info {
+  int tail_states_used = 0, light_status = 0;
+  bool labels_done = false;                                 // the label pass behind the closing light-level launch has written the vectors
+  // the level in hand
+  double t_lvl = 0;
+  BatchDecision dec;
+  bool have_dec = false;
+  u64 P = 0, Q = 0;
+  double pushed_edges = 0;
+  bool plain_level = false, heavy = false;
+  bool pulled_ahead = false;                                // its pull kernels went out behind the totals kernel of the level before, by `planned`
+  SlotPlan planned = {false, -1};
+
+  Sweep(int k_, grb_matrix A_, int max_niter_, SweepOwn* own_, grb_bfs_result* per_) : k(k_), A(A_), max_niter(max_niter_), own(own_), per(per_) {}
+
+  // level words: slot 0 .. nstore are kept for the label pass, four more rotate (batch_slots.hpp)
+  u64* words(int slot) const { return slot < 0 ? nullptr : seen + (size_t)(1 + slot) * z.stride; }
+
+  // results come back through the pinned, host-coherent box the host polls: no copy, no stream wait
+  grb_info wait_box() {
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (__atomic_load_n(&g_box_h[kBatchCounters], __ATOMIC_ACQUIRE) != g_box_seq) {
+      if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
+        GRB_HIP_TRY(hipStreamSynchronize(st));               // a long level, or a fault this wait reports
+        if (__atomic_load_n(&g_box_h[kBatchCounters], __ATOMIC_ACQUIRE) != g_box_seq) return GRB_PANIC;
+      }
+    }
+    return GRB_SUCCESS;
+  }
+
+  grb_info launch_pull(BatchArgs& x) {
     const BatchSlices& B = A->batch_in;
     x.big = in_done ? INT_MAX : batch_big(true);
     x.slices = B.d_slices; x.nslices = B.nslices; x.bigrows = B.d_rows; x.nbig = B.nbig;
     BatchArgs g = x;                                        // the two kernels that gather frontier words: hub j is n + j to them
-    if (H > 0) { g.iind = hot.d_iind; g.hint = hot.d_hint; }
+    if (H > 0) { g.iind = A->batch_hot.d_iind; g.hint = A->batch_hot.d_hint; }
     hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, g);
     GRB_HIP_TRY(hipGetLastError());
     if (B.nslices > 0 && !in_done) {
@@ -1804,326 +1801,391 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
       GRB_HIP_TRY(hipGetLastError());
     }
     return GRB_SUCCESS;
-  };
+  }
+
   // the depth vectors from the kept levels as they stand; go != nullptr: only if that status word says the sweep is over
-  bool labels_done = false;
-  auto launch_labels = [&](const u64* go) -> grb_info {
+  grb_info launch_labels(const u64* go) {
     LabelArgs L;
     L.n = n; L.k = k;
-    L.nstored = nkept;
+    L.nstored = slots.nkept();
     L.seen = seen;
     L.go = go;
     for (int i = 0; i <= kBatchStoreMax; ++i) {
-      L.W[i] = i < nkept ? kept_words[i] : nullptr;
+      const bool kept = i < slots.nkept();
+      L.W[i] = kept ? words(i) : nullptr;
       // discovered by the last allowed iteration: never assigned (bfs.hpp:48-66)
-      L.lab[i] = i < nkept && kept_level[i] + 1 <= max_niter ? (float)(kept_level[i] + 1) : 0.f;
+      L.lab[i] = kept && slots.kept_level(i) + 1 <= max_niter ? (float)(slots.kept_level(i) + 1) : 0.f;
     }
     for (int s = 0; s < 64; ++s) L.label[s] = a.label[s];
     hipLaunchKernelGGL(batch_labels_kernel, dim3(grid), dim3(kBlock), 0, st, L);
     GRB_HIP_TRY(hipGetLastError());
     return GRB_SUCCESS;
-  };
-  BatchDecision dec;
-  bool have_dec = false, pulled_ahead = false;
-  Plan planned = {false, -1, nullptr};
+  }
+
+  grb_info begin(grb_vector* v, const grb_index* sources, int rules_mode, float switchpoint);
+  bool decide();
+  grb_info light_launch();
+  grb_info pull_stage();
+  grb_info push_stage();
+  grb_info totals_and_ahead();
+  grb_info read_level();
+  grb_info finish(int* per_dir, SweepTotals* out);
+};
+}  // namespace
+
+// buffers, the fills, the seed totals, the rule with the first level's decision, the seed kernel
+grb_info Sweep::begin(grb_vector* v, const grb_index* sources, int rules_mode, float switchpoint) {
+  tail_edges = (double)batch_tail_limit();
+  const bool tail_on = tail_edges > 0;
+  GRB_TRY(sweep_resolve(A, own, tail_on, z, buf));
+  // the hot block: H hub words behind the n of every level-word array; the pull kernels' own copies of the CSC indices and
+  // of the hint name hub j as n + j (H = 0: the matrix's arrays as they are)
+  H = A->batch_hot.H;
+  seen = (u64*)buf.words;
+  list = list_carve(buf.list, z);
+  bool clean[4];
+  buf.zero->take(buf.zero_mine, n, z.stride, z.nstore, clean);
+  slots.begin(z.nstore, clean);
+  a.optr = A->csr.ptr; a.oind = A->csr.ind; a.iptr = A->csc.ptr; a.iind = A->csc.ind;
+  a.hint = A->d_pull_hint;
+  a.n = n;
+  a.seen = seen;
+  a.counters = (u64*)buf.cnt;
+  a.k = k;
+  a.ctl = nullptr;
+  a.list_len = nullptr;
+  a.claims = 0; a.stash = 0;
+  a.big_index = nullptr; a.list = nullptr; a.list_fw = nullptr;
+  a.big_out = batch_big(false);
+  d_ctl = a.counters + kBatchSlots * kBatchCounters;        // written by every totals kernel before anybody reads it
+  for (int s = 0; s < 64; ++s) a.label[s] = nullptr;
+  for (int s = 0; s < k; ++s) {
+    GRB_TRY(grb_vector_set_storage(v[s], GRB_DENSE));
+    a.label[s] = (float*)v[s]->d_val;
+  }
+  GRB_TRY(batch_box());
+  // The counter slots are left zero by every totals kernel and the big-row list's length by the commit kernel behind the
+  // owner kernels, so a sweep that ran to its end leaves both zero; on the sweep's own buffers, which nobody else has, that
+  // is remembered, and a sweep that fails in between clears them at the next start.
+  if (!(own && own->small_clean)) {
+    GRB_HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
+    GRB_HIP_TRY(hipMemsetAsync(list.len, 0, kListHeader, st));
+  }
+  if (own) own->small_clean = false;
+  // the light-level launches' state blocks, all of them now: the fill runs while the host is still enqueuing the sweep's
+  // start, not between a level's totals and the launch that waits for it
+  if (tail_on) GRB_HIP_TRY(hipMemsetAsync(buf.tail, 0, kTailStates * z.tail_state, st));
+  GRB_HIP_TRY(hipMemsetAsync(seen, 0, sizeof(u64) * (z.stride + (size_t)n), st));   // seen and the seeds' words (and seen's unused tail)
+  for (int s = 0; s < 64; ++s) seeds.v[s] = s < k ? (Index)sources[s] : 0;
+  reached = (unsigned long long)k;
+  for (int s = 0; s < k; ++s) {
+    nf_s[s] = 1;
+    mf_s[s] = (unsigned long long)(A->h_csr_ptr[(size_t)sources[s] + 1] - A->h_csr_ptr[sources[s]]);
+    edges += mf_s[s];
+    reached_s[s] = 1; edges_s[s] = mf_s[s]; last_prod[s] = 0; dir_s[s] = 0;
+  }
+  // GRB_SPARSE_MATRIX_FORMAT = 1: no CSC storage -- the "CSC" arrays ARE the CSR arrays, and the reference's vxm
+  // is forced to push whatever the mxvmode says (operations.hpp:131-133).  A pull over them would walk out-edges
+  // as if they were in-edges: every source is pushed.
+  const int mode = (A->format != 0 || A->csc_alias) ? GRB_PUSHONLY : rules_mode;
+  grid = stream_grid((long long)ceil_div(n, kWave) * kWave, kBlock);
+  rule.k = k; rule.n = (long long)n; rule.nvals = (long long)A->nvals;
+  rule.mode = mode == GRB_PULLONLY ? kDecidePullOnly : mode == GRB_PUSHONLY ? kDecidePushOnly : kDecidePushPull;
+  rule.switchpoint = switchpoint; rule.budget = knobs.budget; rule.tail_limit = tail_on ? tail_edges : 0.0;
+  rule.finish_limit = knobs.finish_limit;
+  ahead = knobs.ahead && mode != GRB_PUSHONLY;
+  Hcopy = mode == GRB_PUSHONLY ? 0 : H;
   // The first level: when the rule pushes every source (light or not), it runs as a host level whose push is
   // batch_first_level_kernel.  The seeds then need no words of their own -- their labels are written by the seed kernel,
-  // directly -- and Slot(0) takes the level's words.  Any source pulled (pull-only rules, a switch point at 0, sources over
+  // directly -- and slot 0 takes the level's words.  Any source pulled (pull-only rules, a switch point at 0, sources over
   // the budget): the seeds are a stored level and the level runs through the general kernels.
-  bool first_plain = false;
   if (max_niter >= 1) {
     dec = batch_decide(nf_s, mf_s, rule, true);
     have_dec = true;
     first_plain = dec.kind != kDecideDone && dec.qmask == 0;
   }
-  {
-    SeedLabels seed_labels;
-    for (int s = 0; s < 64; ++s) seed_labels.p[s] = a.label[s];
-    hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, seen, first_plain ? (u64*)nullptr : Slot(0), seeds, seed_labels, k);
-    GRB_HIP_TRY(hipGetLastError());
-  }
+  SeedLabels seed_labels;
+  for (int s = 0; s < 64; ++s) seed_labels.p[s] = a.label[s];
+  hipLaunchKernelGGL(batch_seed_kernel, dim3(1), dim3(kBlock), 0, st, seen, first_plain ? (u64*)nullptr : words(0), seeds, seed_labels, k);
+  GRB_HIP_TRY(hipGetLastError());
   if (first_plain) {
     dec.kind = kDecideHost;
-    nkept = 0;                                              // no seed words: plan_slot gives Slot(0) to level 1
-    fcur_words = nullptr;
-    any_direct = true;                                      // the sources' own labels
+    slots.first_plain();                                    // no seed words: the sources' own labels are direct ones
   }
-  GRB_HIP_TRY(hipEventRecord(ev0, st));
-  for (; iter <= max_niter; ++iter) {
-    const double t_lvl = trace ? now_us() : 0.0;
-    if (!have_dec) dec = batch_decide(nf_s, mf_s, rule, true);
-    have_dec = false;
-    if (dec.kind == kDecideDone) break;                     // no live source
-    const u64 P = dec.pmask, Q = dec.qmask;
-    const double pushed_edges = dec.pushed_edges;
-    a.qmask = Q; a.pmask = P;
-    a.claims = 0; a.stash = 0;
-    a.fcur = fcur_words;
-    a.ctl = nullptr;
-    a.list_len = nullptr;
-    a.big_index = nullptr; a.list = nullptr; a.list_fw = nullptr;
-    // ---- every live source pushed and few edges to push: this level and the light ones after it in one launch
-    if (dec.kind == kDecideLight) {
-      pulled_ahead = false;                                 // (launched ahead, the pull kernels found this out and wrote nothing: the plan is dropped)
-      int xi[3];
-      xi[0] = pick(fcur_words, nullptr, nullptr, true);
-      xi[1] = pick(fcur_words, pool[xi[0]], nullptr, true);
-      xi[2] = pick(fcur_words, pool[xi[0]], pool[xi[1]], true);
-      const size_t qcap = z.qcap;
-      const size_t st_bytes = z.tail_state;
-      // the next clean state block; a fifth launch in one sweep and every later one clear the last block for themselves
-      const bool clean_state = tail_states_used < kTailStates;
-      char* const p_state = (char*)p_tail + (size_t)(clean_state ? tail_states_used : kTailStates - 1) * st_bytes;
-      ++tail_states_used;
-      TailArgs t;
-      t.f0 = fcur_words;
-      for (int i = 0; i < 3; ++i) t.X[i] = pool[xi[i]];
-      t.st = (TailState*)p_state;
-      for (int i = 0; i < 3; ++i) t.queue[i] = (u64*)((char*)p_tail + kTailStates * st_bytes) + (size_t)i * qcap;
-      t.box = d_box;
-      t.status = d_ctl + 3;
-      t.seq = ++box_seq;
-      t.iter0 = iter;
-      t.max_niter = max_niter;
-      t.edge_limit = (unsigned long long)tail_edges;
-      t.per_source = per ? 1 : 0;
-      a.direct_labels = 1;
-      if (!clean_state) GRB_HIP_TRY(hipMemsetAsync(p_state, 0, st_bytes, st));
-      for (int i = 0; i < 3; ++i)
-        if (!pool_clean[xi[i]]) GRB_HIP_TRY(hipMemsetAsync(t.X[i], 0, sizeof(u64) * (size_t)n, st));
-      hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
-      GRB_HIP_TRY(hipGetLastError());
-      // the label pass behind it, before the host has the box: it reads the launch's status from the control block and
-      // leaves at once when the sweep goes on.  A light-level launch adds no kept level, so its arguments are known.
-      if (ahead) GRB_TRY(launch_labels(d_ctl + 3));
-      GRB_TRY(wait_box());                                   // any number of levels; GRB_PANIC: a grid barrier gave up
-      const int done = (int)h_box[kBatchCounters + 1];
-      const int status = (int)h_box[kBatchCounters + 4];
-      labels_done = ahead && status != 2;
-      edges += h_box[kBatchCounters + 2];
-      reached += h_box[kBatchCounters + 3];
-      any_left = false;
-      for (int s = 0; s < k; ++s) {
-        nf_s[s] = h_box[2 + 2 * s];
-        mf_s[s] = h_box[3 + 2 * s];
-        if (nf_s[s]) any_left = true;
-        if (per) {
-          reached_s[s] += h_box[kBatchBoxPer + 2 * s];
-          edges_s[s] += h_box[kBatchBoxPer + 2 * s + 1];
-          const int lp = (int)h_box[kBatchBoxPer + 128 + s];
-          if (lp > last_prod[s]) { last_prod[s] = lp; dir_s[s] = 0; }
-        }
-      }
-      levels += done;
-      last_dir = 0;
-      any_direct = true;
-      big_out_new = -1;
-      for (int i = 0; i < 3; ++i) pool_clean[xi[i]] = true;
-      fcur_words = t.X[(done - 1) % 3];                     // the last level run, j = done - 1, wrote X[j % 3]
-      tail_fresh = false;
-      if (status != 0) pool_clean[xi[(done - 1) % 3]] = false;   // the new frontier; every other array was left all-zero
-      if (trace) {
-        u64 ts[64];
-        GRB_HIP_TRY(hipMemcpy(ts, &t.st->ts[0], sizeof(ts), hipMemcpyDeviceToHost));
-        fprintf(stderr, "  launch stamps (us from start; prologue, barrier, then per level: work, flush, barrier):");
-        for (int i = 1; i < 64 && ts[i]; ++i) fprintf(stderr, " %.1f", (double)(ts[i] - ts[0]) * 0.01);
-        fprintf(stderr, "\n");
-      }
-      if (trace)
-        fprintf(stderr, "batch levels %d..%d: one launch (light levels), status %d, pairs %llu  %.1f us\n", iter, iter + done - 1,
-                status, (unsigned long long)h_box[kBatchCounters + 3], now_us() - t_lvl);
-      iter += done - 1;                                     // the level the launch ended on
-      if (status == 0) break;                               // nothing new: the traversals are over
-      continue;                                             // capped (the loop condition ends it) or grown heavy again
+  GRB_HIP_TRY(hipEventRecord(buf.ev0, st));
+  return GRB_SUCCESS;
+}
+
+// the level's decision -- the one the totals kernel of the level before published, else the host's; false: no live source
+bool Sweep::decide() {
+  t_lvl = knobs.trace ? now_us() : 0.0;
+  if (!have_dec) dec = batch_decide(nf_s, mf_s, rule, true);
+  have_dec = false;
+  if (dec.kind == kDecideDone) return false;
+  P = dec.pmask; Q = dec.qmask;
+  pushed_edges = dec.pushed_edges;
+  a.qmask = Q; a.pmask = P;
+  a.claims = 0; a.stash = 0;
+  a.fcur = words(slots.frontier());
+  a.ctl = nullptr;
+  a.list_len = nullptr;
+  a.big_index = nullptr; a.list = nullptr; a.list_fw = nullptr;
+  return true;
+}
+
+// ---- every live source pushed and few edges to push: this level and the light ones after it in one launch.  Leaves iter
+// at the level the launch ended on and light_status at its status: 0 nothing new (the traversals are over), else capped
+// or grown heavy again.
+grb_info Sweep::light_launch() {
+  pulled_ahead = false;                                     // (launched ahead, the pull kernels found this out and wrote nothing: the plan is dropped)
+  int xi[3];
+  slots.light_pick(xi);
+  // the next clean state block; a fifth launch in one sweep and every later one clear the last block for themselves
+  const bool clean_state = tail_states_used < kTailStates;
+  TailArgs t;
+  tail_carve(t, buf.tail, z, clean_state ? tail_states_used : kTailStates - 1);
+  ++tail_states_used;
+  t.f0 = a.fcur;
+  for (int i = 0; i < 3; ++i) t.X[i] = words(xi[i]);
+  t.box = g_box_d;
+  t.status = d_ctl + 3;
+  t.seq = ++g_box_seq;
+  t.iter0 = iter;
+  t.max_niter = max_niter;
+  t.edge_limit = (unsigned long long)tail_edges;
+  t.per_source = per ? 1 : 0;
+  a.direct_labels = 1;
+  if (!clean_state) GRB_HIP_TRY(hipMemsetAsync(t.st, 0, z.tail_state, st));
+  for (int i = 0; i < 3; ++i)
+    if (!slots.clean(xi[i])) GRB_HIP_TRY(hipMemsetAsync(t.X[i], 0, sizeof(u64) * (size_t)n, st));
+  hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
+  GRB_HIP_TRY(hipGetLastError());
+  // the label pass behind it, before the host has the box: it reads the launch's status from the control block and
+  // leaves at once when the sweep goes on.  A light-level launch adds no kept level, so its arguments are known.
+  if (ahead) GRB_TRY(launch_labels(d_ctl + 3));
+  GRB_TRY(wait_box());                                       // any number of levels; GRB_PANIC: a grid barrier gave up
+  const u64* const h_box = g_box_h;
+  const int done = (int)h_box[kBatchCounters + 1];
+  light_status = (int)h_box[kBatchCounters + 4];
+  labels_done = ahead && light_status != 2;
+  edges += h_box[kBatchCounters + 2];
+  reached += h_box[kBatchCounters + 3];
+  any_left = false;
+  for (int s = 0; s < k; ++s) {
+    nf_s[s] = h_box[2 + 2 * s];
+    mf_s[s] = h_box[3 + 2 * s];
+    if (nf_s[s]) any_left = true;
+    if (per) {
+      reached_s[s] += h_box[kBatchBoxPer + 2 * s];
+      edges_s[s] += h_box[kBatchBoxPer + 2 * s + 1];
+      const int lp = (int)h_box[kBatchBoxPer + 128 + s];
+      if (lp > last_prod[s]) { last_prod[s] = lp; dir_s[s] = 0; }
     }
-    const Plan slot = pulled_ahead ? planned : plan_slot(fcur_words);
-    commit_slot(slot, iter);                                // a level of this loop: the plan holds
-    a.fnext = slot.fnext;
-    a.new_label = (float)(iter + 1);
-    a.direct_labels = slot.keep ? 0 : 1;
-    const bool plain_level = first_plain && iter == 1;
-    // heavy: as whoever decided the level published it (the totals kernel, or batch_decide here) -- never derived a second
-    // time, the pull kernels launched ahead have already stashed by it.  The first level's plain launch claims directly.
-    const bool heavy = dec.stash != 0 && !plain_level;
-    a.stash = heavy ? dec.stash : 0ull;
-    if (plain_level) {
-      // the sources' rows, a wave per piece, into Slot(0): the fill at the sweep's start has zeroed it
-      FirstPieces fp;
-      first_level_pieces(A->h_csr_ptr.data(), seeds.v, k, kFirstPiece, fp.pre);
-      hipLaunchKernelGGL(batch_first_level_kernel, dim3(fp.pre[k] > 0 ? (fp.pre[k] + kWavesPerBlock - 1) / kWavesPerBlock : 1u), dim3(kBlock),
-                         0, st, a, seeds, fp);
-      GRB_HIP_TRY(hipGetLastError());
-    } else if (pulled_ahead) {
-      // the pull kernels are already running, or done: for Q == 0 they have zeroed the words
-    } else if (Q) {
-      if (H > 0 && !tail_fresh) {
-        HotCopy hc = {const_cast<u64*>(a.fcur), hot.d_hubs, n, H};
-        hipLaunchKernelGGL(batch_hot_refresh_kernel, dim3(hot_copy_blocks(H)), dim3(kBlock), 0, st, hc);
-        GRB_HIP_TRY(hipGetLastError());
-        if (trace) fprintf(stderr, "sweep hot block: level %d pulls behind a copy launch of its own\n", iter);
-      }
-      GRB_TRY(launch_pull(a));
-    } else if (heavy) {
-      // nothing pulled, but the stash is wanted: the pull kernel's qmask == 0 path writes seen & stash where the fill
-      // wrote zeros (it reads no CSC array, so a push-only matrix takes it too)
-      hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, a);
-      GRB_HIP_TRY(hipGetLastError());
-    } else {
-      GRB_HIP_TRY(hipMemsetAsync(a.fnext, 0, sizeof(u64) * (size_t)n, st));
-    }
-    pulled_ahead = false;
-    if (P && !plain_level) {
-      const BatchSlices& B = A->batch_out;
-      a.big = batch_big(false);
-      a.claims = heavy ? 1 : 0;                             // claims only: the new bits are read back against the stashed old ones
-      a.slices = B.d_slices; a.nslices = B.nslices; a.bigrows = B.d_rows; a.nbig = B.nbig;
-      const bool big_rows = B.nslices > 0 && big_out_new != 0;   // none in the frontier: no slice or owner kernel has anything to do
-      static const bool owner_ok = [] { const char* e = getenv("GRB_BATCH_OWNER"); return !e || atoi(e) != 0; }();
-      static const bool owner_merge = [] { const char* e = getenv("GRB_BATCH_OWNER_MERGE"); return !e || atoi(e) != 0; }();
-      const bool owners = big_rows && heavy && owner_ok && B.d_range_off && B.d_big_index;
-      int* d_list = (int*)((char*)p_list + kListHeader);
-      u64* d_list_fw = (u64*)((char*)p_list + kListHeader + z.list_ids);
-      if (owners) {
-        // heavy level: the big rows' edges are settled by the owners of their destination ranges, in LDS; the push kernel
-        // lists the big frontier rows it skips
-        a.big_index = B.d_big_index; a.list = d_list; a.list_fw = d_list_fw;
-        a.list_len = d_count;                                // zero here; the commit kernel below puts it back to zero
-      }
-      hipLaunchKernelGGL(batch_push_kernel, dim3(grid), dim3(kBlock), 0, st, a);
-      GRB_HIP_TRY(hipGetLastError());
-      a.big_index = nullptr;
-      if (owners) {
-        const int S = (int)own_off_stride(B.nranges);
-        // Few narrow ranges (fewer than CUs: a launch of them cannot occupy the chip, whatever its occupancy per CU -- on
-        // RMAT-22 it is ONE workgroup, the hub range, walking its pieces of every listed row for 20 us while the wide
-        // instance waits): one launch of the wide instance over all ranges, which handles a range of <= 2 Ki rows as it
-        // stands.  The ids are taken from their start, narrow ranges first, so the long hub workgroups start first.  The
-        // XCD dealing of make_slices holds up to a rotation: the wide part's eighths land on XCDs rotated by nsmall mod 8,
-        // each still contiguous on one XCD.  GRB_BATCH_OWNER_MERGE=0: always the two launches (A/B runs, tests).
-        const bool merged = owner_merge && B.nsmall > 0 && B.nranges > B.nsmall && B.nsmall < c.num_cu;
-        if (merged) {
-          hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(B.nranges), dim3(1024), 0, st, a,
-                             (const Index*)B.d_range_off, S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
-                             (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
-        } else {
-          if (B.nsmall > 0)
-            hipLaunchKernelGGL((batch_push_owner_kernel<kOwnSmallRows, 512>), dim3(B.nsmall), dim3(512), 0, st, a, (const Index*)B.d_range_off,
-                               S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
-                               (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
-          if (B.nranges > B.nsmall)
-            hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(B.nranges - B.nsmall), dim3(1024), 0, st, a,
-                               (const Index*)B.d_range_off, S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
-                               (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + B.nsmall);
-        }
-        GRB_HIP_TRY(hipGetLastError());
-        if (trace) {
-          unsigned int hc = 0, parts[kListSegs * kListLenStride];
-          GRB_HIP_TRY(hipMemcpy(parts, d_count, kListHeader, hipMemcpyDeviceToHost));
-          for (int g = 0; g < kListSegs; ++g) hc += parts[g * kListLenStride];
-          fprintf(stderr, "batch level %d: owner-computes push, %u of %d big rows in the frontier, %d ranges (%d narrow, %d wide)\n", iter, hc, B.nbig,
-                  B.nranges, B.nsmall, B.nranges - B.nsmall);
-          const int launches = merged ? 1 : (B.nsmall > 0 ? 1 : 0) + (B.nranges > B.nsmall ? 1 : 0);
-          fprintf(stderr, "batch level %d: range owners in %d launch%s\n", iter, launches, launches == 1 ? "" : "es");
-        }
-      } else if (big_rows) {
-        hipLaunchKernelGGL(batch_push_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
-                           0, st, a);
-        GRB_HIP_TRY(hipGetLastError());
-      }
-      hipLaunchKernelGGL(batch_push_commit_kernel, dim3(grid), dim3(kBlock), 0, st, a);
-      GRB_HIP_TRY(hipGetLastError());
-      if (trace)
-        fprintf(stderr, "batch push stage of level %d: batch_push_kernel, %sbatch_push_commit_kernel\n", iter,
-                owners ? "range owners, " : big_rows ? "batch_push_slices_kernel, " : "");
-    }
-    // the totals come back through a pinned, host-coherent box the host polls: no copy, no stream wait
-    DecideArgs da;
-    da.rule = rule;
-    da.iteration_left = iter + 1 <= max_niter ? 1 : 0;
-    da.open_complete = P == 0 && Q != 0 ? 1 : 0;            // every live source pulled: the level's U covers them all
-    da.ctl = d_ctl;
-    const HotCopy hc = {a.fnext, hot.d_hubs, n, Hcopy};      // the level's words are complete here: their tail, for the next level's pull
-    hipLaunchKernelGGL(batch_totals_kernel, dim3(1 + hot_copy_blocks(Hcopy)), dim3(kBlock), 0, st, a.counters, d_box, ++box_seq, da, hc);
+  }
+  levels += done;
+  last_dir = 0;
+  big_out_new = -1;
+  slots.light_done(xi, done, light_status);                 // the last level run, j = done - 1, wrote X[j % 3]: the new frontier
+  tail_fresh = false;
+  if (knobs.trace) {
+    u64 ts[64];
+    GRB_HIP_TRY(hipMemcpy(ts, &t.st->ts[0], sizeof(ts), hipMemcpyDeviceToHost));
+    fprintf(stderr, "  launch stamps (us from start; prologue, barrier, then per level: work, flush, barrier):");
+    for (int i = 1; i < 64 && ts[i]; ++i) fprintf(stderr, " %.1f", (double)(ts[i] - ts[0]) * 0.01);
+    fprintf(stderr, "\n");
+    fprintf(stderr, "batch levels %d..%d: one launch (light levels), status %d, pairs %llu  %.1f us\n", iter, iter + done - 1,
+            light_status, (unsigned long long)h_box[kBatchCounters + 3], now_us() - t_lvl);
+  }
+  iter += done - 1;
+  return GRB_SUCCESS;
+}
+
+// ---- a level of the host loop.  Its words' place, then the pull: the first level's plain launch, the kernels already
+// launched ahead, the pull kernels for Q, the pull kernel's stash path, or a fill.
+grb_info Sweep::pull_stage() {
+  const SlotPlan slot = pulled_ahead ? planned : slots.plan();
+  slots.commit(slot, iter);                                 // a level of this loop: the plan holds
+  a.fnext = words(slot.slot);
+  a.new_label = (float)(iter + 1);
+  a.direct_labels = slot.keep ? 0 : 1;
+  plain_level = first_plain && iter == 1;
+  // heavy: as whoever decided the level published it (the totals kernel, or batch_decide here) -- never derived a second
+  // time, the pull kernels launched ahead have already stashed by it.  The first level's plain launch claims directly.
+  heavy = dec.stash != 0 && !plain_level;
+  a.stash = heavy ? dec.stash : 0ull;
+  if (plain_level) {
+    // the sources' rows, a wave per piece, into slot 0: the fill at the sweep's start has zeroed it
+    FirstPieces fp;
+    first_level_pieces(A->h_csr_ptr.data(), seeds.v, k, kFirstPiece, fp.pre);
+    hipLaunchKernelGGL(batch_first_level_kernel, dim3(fp.pre[k] > 0 ? (fp.pre[k] + kWavesPerBlock - 1) / kWavesPerBlock : 1u), dim3(kBlock),
+                       0, st, a, seeds, fp);
     GRB_HIP_TRY(hipGetLastError());
-    tail_fresh = true;
-    if (ahead && iter + 1 <= max_niter) {
-      // the next level's pull kernels, behind the totals kernel that decides whether and on which bits they run
-      BatchArgs an = a;
-      an.fcur = a.fnext;
-      planned = plan_slot(an.fcur);
-      an.fnext = planned.fnext;
-      an.new_label = (float)(iter + 2);
-      an.direct_labels = planned.keep ? 0 : 1;
-      an.claims = 0; an.stash = 0;
-      an.list_len = nullptr;
-      an.qmask = 0; an.pmask = 0;
-      an.ctl = d_ctl;
-      GRB_TRY(launch_pull(an));
-      pulled_ahead = true;
+  } else if (pulled_ahead) {
+    // the pull kernels are already running, or done: for Q == 0 they have zeroed the words
+  } else if (Q) {
+    if (H > 0 && !tail_fresh) {
+      HotCopy hc = {const_cast<u64*>(a.fcur), A->batch_hot.d_hubs, n, H};
+      hipLaunchKernelGGL(batch_hot_refresh_kernel, dim3(hot_copy_blocks(H)), dim3(kBlock), 0, st, hc);
+      GRB_HIP_TRY(hipGetLastError());
+      if (knobs.trace) fprintf(stderr, "sweep hot block: level %d pulls behind a copy launch of its own\n", iter);
     }
-    GRB_TRY(wait_box());
-    u64 t[kBatchCounters];
-    for (int j = 0; j < kBatchCounters; ++j) t[j] = __atomic_load_n(&h_box[j], __ATOMIC_RELAXED);
-    dec.qmask = __atomic_load_n(&h_box[kBoxDecision], __ATOMIC_RELAXED);
-    dec.pmask = __atomic_load_n(&h_box[kBoxDecision + 1], __ATOMIC_RELAXED);
-    dec.kind = (int)__atomic_load_n(&h_box[kBoxDecision + 2], __ATOMIC_RELAXED);
-    dec.stash = __atomic_load_n(&h_box[kBoxDecision + 3], __ATOMIC_RELAXED);
-    have_dec = true;
-    if ((t[kCntInOpen] & kInOpenCounted) && (t[kCntInOpen] & (kInOpenCounted - 1)) == 0) in_done = true;
-    big_out_new = (long long)t[kCntBigOut];
-    ++levels;
-    last_dir = Q ? 1 : 0;
-    fcur_words = a.fnext;
-    any_left = false;
-    u64 pairs = 0;
-    for (int s = 0; s < k; ++s) {
-      nf_s[s] = t[2 + 2 * s];
-      mf_s[s] = t[3 + 2 * s];
-      pairs += nf_s[s];
-      reached += nf_s[s];
-      edges += mf_s[s];
-      reached_s[s] += nf_s[s];
-      edges_s[s] += mf_s[s];
-      if (nf_s[s]) { any_left = true; last_prod[s] = iter; dir_s[s] = (int)((Q >> s) & 1ull); }
-    }
-    if (trace)
-      fprintf(stderr, "batch level %d: pull %d sources, push %d (%.0f edges, %s) -> vertices %llu pairs %llu, big in-rows open %s%llu, "
-              "big out-rows found %lld, next level %s  %.1f us, U %llu%s\n",
-              iter, __builtin_popcountll(Q), __builtin_popcountll(P), pushed_edges, a.claims ? "claims" : "direct", t[0],
-              pairs, (t[kCntInOpen] & kInOpenCounted) ? "" : "(not counted) ", t[kCntInOpen] & (kInOpenCounted - 1), big_out_new,
-              dec.kind == kDecideHost ? (pulled_ahead ? "pulled ahead" : "host") : dec.kind == kDecideLight ? "light" : "none",
-              now_us() - t_lvl, t[kCntOpenU] & (kOpenUComplete - 1), (t[kCntOpenU] & kOpenUComplete) ? "" : " (not complete)");
-    dec.pushed_edges = 0;
-    for (int s = 0; s < k; ++s) if ((dec.pmask >> s) & 1ull) dec.pushed_edges += (double)mf_s[s];
-    if (!any_left) break;
+    GRB_TRY(launch_pull(a));
+  } else if (heavy) {
+    // nothing pulled, but the stash is wanted: the pull kernel's qmask == 0 path writes seen & stash where the fill
+    // wrote zeros (it reads no CSC array, so a push-only matrix takes it too)
+    hipLaunchKernelGGL(batch_pull_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+    GRB_HIP_TRY(hipGetLastError());
+  } else {
+    GRB_HIP_TRY(hipMemsetAsync(a.fnext, 0, sizeof(u64) * (size_t)n, st));
   }
+  pulled_ahead = false;
+  return GRB_SUCCESS;
+}
+
+// the level's push, for the sources in P: the push kernel, the big rows by their ranges' owners or by slices, the commit
+grb_info Sweep::push_stage() {
+  if (!P || plain_level) return GRB_SUCCESS;
+  const BatchSlices& B = A->batch_out;
+  a.big = batch_big(false);
+  a.claims = heavy ? 1 : 0;                                 // claims only: the new bits are read back against the stashed old ones
+  a.slices = B.d_slices; a.nslices = B.nslices; a.bigrows = B.d_rows; a.nbig = B.nbig;
+  const bool big_rows = B.nslices > 0 && big_out_new != 0;  // none in the frontier: no slice or owner kernel has anything to do
+  const bool owners = big_rows && heavy && knobs.owner && B.d_range_off && B.d_big_index;
+  if (owners) {
+    // heavy level: the big rows' edges are settled by the owners of their destination ranges, in LDS; the push kernel
+    // lists the big frontier rows it skips
+    a.big_index = B.d_big_index; a.list = list.ids; a.list_fw = list.words;
+    a.list_len = list.len;                                  // zero here; the commit kernel below puts it back to zero
+  }
+  hipLaunchKernelGGL(batch_push_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+  GRB_HIP_TRY(hipGetLastError());
+  a.big_index = nullptr;
+  if (owners) {
+    // Few narrow ranges (fewer than CUs: a launch of them cannot occupy the chip, whatever its occupancy per CU -- on
+    // RMAT-22 it is ONE workgroup, the hub range, walking its pieces of every listed row for 20 us while the wide
+    // instance waits): one launch of the wide instance over all ranges, which handles a range of <= 2 Ki rows as it
+    // stands.  The ids are taken from their start, narrow ranges first, so the long hub workgroups start first.  The
+    // XCD dealing of make_slices holds up to a rotation: the wide part's eighths land on XCDs rotated by nsmall mod 8,
+    // each still contiguous on one XCD.  GRB_BATCH_OWNER_MERGE=0: always the two launches (A/B runs, tests).
+    const bool merged = knobs.owner_merge && B.nsmall > 0 && B.nranges > B.nsmall && B.nsmall < c.num_cu;
+    if (merged) {
+      launch_owners<kOwnRows, 1024>(a, B, list, 0, B.nranges, st);
+    } else {
+      if (B.nsmall > 0) launch_owners<kOwnSmallRows, 512>(a, B, list, 0, B.nsmall, st);
+      if (B.nranges > B.nsmall) launch_owners<kOwnRows, 1024>(a, B, list, B.nsmall, B.nranges - B.nsmall, st);
+    }
+    GRB_HIP_TRY(hipGetLastError());
+    if (knobs.trace) {
+      unsigned int hc = 0, parts[kListSegs * kListLenStride];
+      GRB_HIP_TRY(hipMemcpy(parts, list.len, kListHeader, hipMemcpyDeviceToHost));
+      for (int g = 0; g < kListSegs; ++g) hc += parts[g * kListLenStride];
+      fprintf(stderr, "batch level %d: owner-computes push, %u of %d big rows in the frontier, %d ranges (%d narrow, %d wide)\n", iter, hc, B.nbig,
+              B.nranges, B.nsmall, B.nranges - B.nsmall);
+      const int launches = merged ? 1 : (B.nsmall > 0 ? 1 : 0) + (B.nranges > B.nsmall ? 1 : 0);
+      fprintf(stderr, "batch level %d: range owners in %d launch%s\n", iter, launches, launches == 1 ? "" : "es");
+    }
+  } else if (big_rows) {
+    hipLaunchKernelGGL(batch_push_slices_kernel, dim3(stream_grid((long long)B.nslices * kWave, kBlock)), dim3(kBlock),
+                       0, st, a);
+    GRB_HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(batch_push_commit_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+  GRB_HIP_TRY(hipGetLastError());
+  if (knobs.trace)
+    fprintf(stderr, "batch push stage of level %d: batch_push_kernel, %sbatch_push_commit_kernel\n", iter,
+            owners ? "range owners, " : big_rows ? "batch_push_slices_kernel, " : "");
+  return GRB_SUCCESS;
+}
+
+// the level's totals and the next level's decision, on the device; behind them the next level's pull, launched ahead
+grb_info Sweep::totals_and_ahead() {
+  DecideArgs da;
+  da.rule = rule;
+  da.iteration_left = iter + 1 <= max_niter ? 1 : 0;
+  da.open_complete = P == 0 && Q != 0 ? 1 : 0;              // every live source pulled: the level's U covers them all
+  da.ctl = d_ctl;
+  const HotCopy hc = {a.fnext, A->batch_hot.d_hubs, n, Hcopy};   // the level's words are complete here: their tail, for the next level's pull
+  hipLaunchKernelGGL(batch_totals_kernel, dim3(1 + hot_copy_blocks(Hcopy)), dim3(kBlock), 0, st, a.counters, g_box_d, ++g_box_seq, da, hc);
+  GRB_HIP_TRY(hipGetLastError());
+  tail_fresh = true;
+  if (ahead && iter + 1 <= max_niter) {
+    // the next level's pull kernels, behind the totals kernel that decides whether and on which bits they run
+    BatchArgs an = a;
+    an.fcur = a.fnext;
+    planned = slots.plan();
+    an.fnext = words(planned.slot);
+    an.new_label = (float)(iter + 2);
+    an.direct_labels = planned.keep ? 0 : 1;
+    an.claims = 0; an.stash = 0;
+    an.list_len = nullptr;
+    an.qmask = 0; an.pmask = 0;
+    an.ctl = d_ctl;
+    GRB_TRY(launch_pull(an));
+    pulled_ahead = true;
+  }
+  return GRB_SUCCESS;
+}
+
+// the host blocks here: the level's counters and the next level's decision out of the box
+grb_info Sweep::read_level() {
+  GRB_TRY(wait_box());
+  const u64* const h_box = g_box_h;
+  u64 t[kBatchCounters];
+  for (int j = 0; j < kBatchCounters; ++j) t[j] = __atomic_load_n(&h_box[j], __ATOMIC_RELAXED);
+  dec.qmask = __atomic_load_n(&h_box[kBoxDecision], __ATOMIC_RELAXED);
+  dec.pmask = __atomic_load_n(&h_box[kBoxDecision + 1], __ATOMIC_RELAXED);
+  dec.kind = (int)__atomic_load_n(&h_box[kBoxDecision + 2], __ATOMIC_RELAXED);
+  dec.stash = __atomic_load_n(&h_box[kBoxDecision + 3], __ATOMIC_RELAXED);
+  have_dec = true;
+  if ((t[kCntInOpen] & kInOpenCounted) && (t[kCntInOpen] & (kInOpenCounted - 1)) == 0) in_done = true;
+  big_out_new = (long long)t[kCntBigOut];
+  ++levels;
+  last_dir = Q ? 1 : 0;
+  any_left = false;
+  u64 pairs = 0;
+  for (int s = 0; s < k; ++s) {
+    nf_s[s] = t[2 + 2 * s];
+    mf_s[s] = t[3 + 2 * s];
+    pairs += nf_s[s];
+    reached += nf_s[s];
+    edges += mf_s[s];
+    reached_s[s] += nf_s[s];
+    edges_s[s] += mf_s[s];
+    if (nf_s[s]) { any_left = true; last_prod[s] = iter; dir_s[s] = (int)((Q >> s) & 1ull); }
+  }
+  if (knobs.trace)
+    fprintf(stderr, "batch level %d: pull %d sources, push %d (%.0f edges, %s) -> vertices %llu pairs %llu, big in-rows open %s%llu, "
+            "big out-rows found %lld, next level %s  %.1f us, U %llu%s\n",
+            iter, __builtin_popcountll(Q), __builtin_popcountll(P), pushed_edges, a.claims ? "claims" : "direct", t[0],
+            pairs, (t[kCntInOpen] & kInOpenCounted) ? "" : "(not counted) ", t[kCntInOpen] & (kInOpenCounted - 1), big_out_new,
+            dec.kind == kDecideHost ? (pulled_ahead ? "pulled ahead" : "host") : dec.kind == kDecideLight ? "light" : "none",
+            now_us() - t_lvl, t[kCntOpenU] & (kOpenUComplete - 1), (t[kCntOpenU] & kOpenUComplete) ? "" : " (not complete)");
+  dec.pushed_edges = 0;
+  for (int s = 0; s < k; ++s) if ((dec.pmask >> s) & 1ull) dec.pushed_edges += (double)mf_s[s];
+  return GRB_SUCCESS;
+}
+
+// the depth vectors, the sweep's time, what the next sweep may rely on, the results
+grb_info Sweep::finish(int* per_dir, SweepTotals* out) {
   const bool hit_cap = iter > max_niter && any_left;
-  // ---- the depth vectors (unless the pass enqueued behind the closing light-level launch has written them)
+  // (unless the pass enqueued behind the closing light-level launch has written them)
   if (!labels_done) GRB_TRY(launch_labels(nullptr));
-  if (hit_cap && any_direct) {
+  if (hit_cap && slots.any_direct()) {
     // vertices discovered by the last allowed iteration are never assigned by the reference loop (bfs.hpp:48-66)
     hipLaunchKernelGGL(batch_unlabel_kernel, dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, a,
                        (float)(max_niter + 1));
     GRB_HIP_TRY(hipGetLastError());
   }
-  GRB_HIP_TRY(hipEventRecord(ev1, st));
-  GRB_HIP_TRY(hipEventSynchronize(ev1));                    // the labels are in place
-  GRB_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  float ms = 0.f;
+  GRB_HIP_TRY(hipEventRecord(buf.ev1, st));
+  GRB_HIP_TRY(hipEventSynchronize(buf.ev1));                // the labels are in place
+  GRB_HIP_TRY(hipEventElapsedTime(&ms, buf.ev0, buf.ev1));
+  buf.zero->keep(n, z.stride, z.nstore, slots.clean_flags());
   if (own) {
     own->small_clean = true;
-    own->clean_valid = true;
-    own->clean_n = n;
-    own->clean_stride = stride;
-    own->clean_nstore = nstore;
-    for (int i = 0; i < 4; ++i) own->clean[i] = pool_clean[i];
   } else {
-    kept_pool.valid = true;
-    kept_pool.epoch = c.slot_epoch[7];
-    kept_pool.ptr = p_words;
-    kept_pool.n = n;
-    kept_pool.stride = stride;
-    kept_pool.nstore = nstore;
-    for (int i = 0; i < 4; ++i) kept_pool.clean[i] = pool_clean[i];
+    g_sweep_scratch.epoch = c.slot_epoch[7];
+    g_sweep_scratch.ptr = buf.words;
   }
   if (per)
     for (int s = 0; s < k; ++s) {
@@ -2136,6 +2198,32 @@ static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index*
     }
   out->levels = levels; out->last_dir = last_dir; out->edges = edges; out->reached = reached; out->hit_cap = hit_cap; out->ms = ms;
   return GRB_SUCCESS;
+}
+
+// k traversals of A (both orientations, the pull hint and the slice tables ready) from sources[] into v[] under the rules
+// (mode, max_niter, switchpoint).  per != nullptr: every source's own result block, as its own one-launch traversal
+// would report it -- reached = 1 + its discoveries, edges = its out-degree + theirs, levels = the iterations its own loop
+// runs (up to and including the first that discovers nothing, at most max_niter), tight_ms = the sweep's device time / k;
+// per_dir[s] = 1 when the source's last productive level was pulled.  Timed with HIP events of its own (the library's
+// timer belongs to the caller); returns after the label pass has completed.
+static grb_info batch_sweep(grb_vector* v, int k, grb_matrix A, const grb_index* sources, int rules_mode, int max_niter,
+                            float switchpoint, SweepOwn* own, grb_bfs_result* per, int* per_dir, SweepTotals* out) {
+  Sweep s(k, A, max_niter, own, per);
+  GRB_TRY(s.begin(v, sources, rules_mode, switchpoint));
+  for (; s.iter <= max_niter; ++s.iter) {
+    if (!s.decide()) break;                                 // no live source
+    if (s.dec.kind == kDecideLight) {
+      GRB_TRY(s.light_launch());
+      if (s.light_status == 0) break;                       // nothing new: the traversals are over
+      continue;                                             // capped (the loop condition ends it) or grown heavy again
+    }
+    GRB_TRY(s.pull_stage());
+    GRB_TRY(s.push_stage());
+    GRB_TRY(s.totals_and_ahead());
+    GRB_TRY(s.read_level());
+    if (!s.any_left) break;
+  }
+  return s.finish(per_dir, out);
 }
 
 // ---- the sweep as the traversal queue uses it (bfs_persist.hip: bfs_co_flush) ------------------------------------------
@@ -2156,11 +2244,9 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   a.big_out = batch_big(false);
   a.counters = (u64*)own->cnt;
   a.direct_labels = 1;
+  const ListBlock list = list_carve(own->list, z);
   GRB_HIP_TRY(hipMemsetAsync(own->cnt, 0, sizeof(u64) * kBatchSlots * kBatchCounters, st));
-  GRB_HIP_TRY(hipMemsetAsync(own->list, 0, kListHeader, st));   // the list's lengths: 0
-  unsigned int* d_count = (unsigned int*)own->list;
-  int* d_list = (int*)((char*)own->list + kListHeader);
-  u64* d_list_fw = (u64*)((char*)own->list + kListHeader + z.list_ids);
+  GRB_HIP_TRY(hipMemsetAsync(list.len, 0, kListHeader, st));   // the list's lengths: 0
   if (!own->warmed) {
     SeedSources none;
     memset(&none, 0, sizeof(none));
@@ -2186,17 +2272,14 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
     TailArgs t;
     memset(&t, 0, sizeof(t));
     t.f0 = a.fcur;
-    for (int i = 0; i < 3; ++i) {
-      t.X[i] = a.seen;
-      t.queue[i] = (u64*)((char*)own->tail + kTailStates * z.tail_state) + (size_t)i * z.qcap;
-    }
-    t.st = (TailState*)own->tail;
+    for (int i = 0; i < 3; ++i) t.X[i] = a.seen;
+    tail_carve(t, own->tail, z, 0);
     t.box = g_box_d;
     t.status = a.counters + kBatchSlots * kBatchCounters + 3;
     t.seq = ++g_box_seq;
     t.iter0 = 1; t.max_niter = 1;
     t.per_source = 1;
-    GRB_HIP_TRY(hipMemsetAsync(own->tail, 0, z.tail_state, st));
+    GRB_HIP_TRY(hipMemsetAsync(t.st, 0, z.tail_state, st));
     hipLaunchKernelGGL(batch_tail_kernel, dim3(c.num_cu), dim3(kPThreads), 0, st, a, t);
     GRB_HIP_TRY(hipGetLastError());
     DecideArgs da;
@@ -2218,17 +2301,12 @@ static grb_info sweep_warm(grb_matrix A, SweepOwn* own, const SweepSizes& z) {
   const BatchSlices& B = A->batch_out;
   if (B.d_range_off && B.nranges > 0) {
     a.nbig = B.nbig;
-    const int S = (int)own_off_stride(B.nranges);
     if (B.nsmall > 0 && !own->warmed_own_small) {
-      hipLaunchKernelGGL((batch_push_owner_kernel<kOwnSmallRows, 512>), dim3(1), dim3(512), 0, st, a, (const Index*)B.d_range_off,
-                         S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
-                         (const Index*)B.d_range_bounds, (const int*)B.d_range_ids);
+      launch_owners<kOwnSmallRows, 512>(a, B, list, 0, 1, st);
       own->warmed_own_small = true;
     }
     if (B.nranges > B.nsmall && !own->warmed_own_wide) {
-      hipLaunchKernelGGL((batch_push_owner_kernel<kOwnRows, 1024>), dim3(1), dim3(1024), 0, st, a,
-                         (const Index*)B.d_range_off, S, (const int*)d_list, (const u64*)d_list_fw, (const unsigned int*)d_count,
-                         (const Index*)B.d_range_bounds, (const int*)B.d_range_ids + B.nsmall);
+      launch_owners<kOwnRows, 1024>(a, B, list, B.nsmall, 1, st);
       own->warmed_own_wide = true;
     }
     GRB_HIP_TRY(hipGetLastError());
@@ -2308,7 +2386,7 @@ grb_info grb::bfs_sweep_provision(grb_matrix A) {
   SweepSizes z = sweep_sizes(A);
   if (o.words_cap < z.words || o.tail_cap < z.tail || o.list_cap < z.list) {
     if (hipStreamSynchronize(c.stream) != hipSuccess) return failed(GRB_PANIC);   // (an earlier sweep may still read the old ones)
-    o.clean_valid = false;
+    o.zero.valid = false;
     o.small_clean = false;
     i = sweep_grow(&o.words, &o.words_cap, z.words);
     if (i != GRB_SUCCESS && A->batch_hot.H > 0) {            // no room for the tails: without the hot block, then
@@ -2340,8 +2418,7 @@ grb_info grb::bfs_sweep_routed(grb_vector* v, int k, grb_matrix A, const grb_ind
                                grb_bfs_result* per, int* per_dir) {
   if (k < 1 || k > 64 || A->sweep_state != 1) return GRB_NOT_IMPLEMENTED;
   SweepTotals tot;
-  const grb_info i = batch_sweep(v, k, A, sources, mode, max_niter, switchpoint, &g_sweep, per, per_dir, &tot);
-  if (i != GRB_SUCCESS) { g_sweep.clean_valid = false; return i; }
+  GRB_TRY(batch_sweep(v, k, A, sources, mode, max_niter, switchpoint, &g_sweep, per, per_dir, &tot));
   return tot.hit_cap ? GRB_NOT_IMPLEMENTED : GRB_SUCCESS;
 }
 

@@ -135,6 +135,40 @@ def test_batch_max_niter_cap_and_errors(hb, fx):
     assert g.bfs_batch([g.Vector(n) for _ in range(65)], A, [0] * 65, d)[0] == g.GrB_INVALID_VALUE
 
 
+def test_batch_levels_beyond_the_kept_slots(hb):
+    """A chain of 48 vertices from both ends and the middle, every level through the host loop: beyond 17 kept levels
+    the words rotate and the levels label directly, and a cap at 20 falls on such a level (its labels are taken back).
+    Each case twice in a row: the second sweep starts from the arrays the first one remembered as zero."""
+    from graphblast_amd.graphgen import finalize_edges
+    g = hb.g
+    n = 48
+    gr = finalize_edges(np.arange(n - 1), np.arange(1, n), n, symmetrize=True)
+    ptr, ind = gr["csr"]
+    deg = np.diff(ptr)
+    A = g.Matrix(n, n)
+    assert A.build_csr(ptr, ind, np.ones(ind.size, F)) == 0
+    srcs = [0, n - 1, n // 2]
+    full = [np.abs(np.arange(n) - s_).astype(F) + 1 for s_ in srcs]
+    before = g.bfs_batch_set_tail(0)
+    try:
+        for mode in (0, 1, 2):
+            for cap in (None, 20):
+                args = dict(mxvmode=mode) if cap is None else dict(mxvmode=mode, max_niter=cap)
+                want = [lab if cap is None else np.where(lab <= cap, lab, 0) for lab in full]
+                for rep in range(2):
+                    got, res, _ = run_batch(hb, A, n, srcs, **args)
+                    for s_, x, y in zip(srcs, got, want):
+                        assert np.array_equal(x, y), (mode, cap, rep, s_)
+                    # the loop runs until a level finds nothing (the 48th from an end), or to the cap
+                    assert res["levels"] == (n if cap is None else cap), (mode, cap, rep, res)
+                    if cap is None:
+                        assert res["reached"] == 3 * n and res["edges_traversed"] == 3 * int(deg.sum()), (mode, rep, res)
+                    else:                                           # under a cap the tally would count unassigned vertices
+                        assert res["reached"] == -1 and res["edges_traversed"] == -1, (mode, rep, res)
+    finally:
+        g.bfs_batch_set_tail(before)
+
+
 def test_light_levels_in_one_launch_equal_the_host_loop(hb):
     """The levels grb_bfs_batch runs inside its one co-resident launch (every live source pushed, few out-edges:
     the first level, the tail, every level of a high-diameter graph) against the same sweep with the launch
