@@ -81,6 +81,12 @@ class ContractResult(C.Structure):
                 ("dropped", C.c_int32), ("largest", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
 
 
+class LouvainResult(C.Structure):
+    _fields_ = [("qn", C.c_int64), ("w", C.c_int64), ("moves", C.c_int64), ("proposals", C.c_int64),
+                ("modularity", C.c_double), ("levels", C.c_int32), ("rounds", C.c_int32), ("communities", C.c_int32),
+                ("passes", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
+
+
 class MaxflowResult(C.Structure):
     _fields_ = [("value", C.c_int64), ("arcs", C.c_int64), ("flow_arcs", C.c_int64), ("sink_side", C.c_int64),
                 ("cut_arcs", C.c_int64), ("cut_capacity", C.c_int64), ("rounds", C.c_int32), ("global_relabels", C.c_int32),
@@ -266,6 +272,7 @@ _SIGS = {
     "grb_matching": [_vp, _vp, _vp, _i, C.c_uint32, _vp, C.POINTER(MatchingResult)],
     "grb_relabel": [_vp, _vp, _i, C.POINTER(C.c_int32), _vp],
     "grb_contract": [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(ContractResult)],
+    "grb_louvain": [_vp, _vp, _i, _i, _i, _vp, C.POINTER(LouvainResult)],
     "grb_maxflow": [_vp, _vp, _vp, C.c_int64, C.c_int64, _i, _vp, C.POINTER(MaxflowResult)],
     "grb_bcc": [_vp, _vp, _vp, _i, _vp, C.POINTER(BccResult)],
     "grb_tc_set_product": [_i],

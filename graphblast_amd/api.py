@@ -964,6 +964,40 @@ def contract(Cm, sizes, A, map, op, loops, desc):
                       largest=res.largest, launches=res.launches, loop_ms=res.loop_ms)
 
 
+def louvain(labels, A, weighted, max_levels, max_rounds, desc):
+    """grb_louvain: labels = the communities of A's undirected graph by Louvain modularity optimisation, deterministic and in
+    exact integers.  A is n x n, f32 or i32, symmetric in structure and values.  weighted = 1 reads the values: i32 >= 0, f32
+    a non-negative integer value <= 2^24 with -0.0 = +0.0 (negative, fractional, NaN, inf -> GrB_INVALID_VALUE); weighted = 0
+    never reads them, every stored entry weighs 1.  A stored zero is an entry of weight 0, a diagonal entry a loop.  W = the
+    sum of all stored weights, each entry once as stored, must be <= 2^31 - 1.  For a partition c, in(x) = the stored weight
+    inside community x, tot(x) = the sum of the row sums k(v) of its members, QN = W * sum in(x) - sum tot(x)^2 and
+    Q = QN / W^2; QN is invariant under contraction with loops kept.  A level starts from c(v) = v and runs rounds: every
+    vertex with an off-diagonal entry proposes the neighbouring community with the largest gain
+    W e(v, x) - k(v) tot(x) - stay, the smallest x on a tie, only if the gain is > 0; every proposal claims its source and its
+    destination, a community's winner is the claimant with the largest gain, the smallest v on a tie; (v -> d, g) is accepted
+    iff v wins c(v), and v wins d or d's winner itself enters d and g > k(v) (K(d) - k(v)) with K(d) the k of all proposers
+    to d; all accepted moves are applied at once.  Every accepted round strictly increases QN.  A round without proposals
+    ends the level (it counts in rounds), and so does max_rounds.  Between levels the graph is contracted (grb_relabel, then
+    grb_contract with PLUS and loops kept); the call stops after the first level that accepted no move (it counts in levels)
+    or after max_levels.  labels is an i32 vector of size n that becomes dense: labels[v] = the smallest original vertex
+    number in v's final community, as in cc, scc and msf.  No descriptor field is read.  A level is one launch on the device;
+    every vertex is evaluated in every round, and a path is the worst case (equal gains serialise on the smallest-v tie).
+    Only the CSR is read: with a CSC of its own an A whose structure (with weighted = 1: or values) is not symmetric ->
+    GrB_INVALID_VALUE, without one (a product result, the CSR-only format) the caller vouches for it and the call stays
+    bounded.  A bad weight, W > 2^31 - 1, weighted outside {0, 1}, max_levels < 1 or max_rounds < 1 -> GrB_INVALID_VALUE.  A
+    null or unbuilt argument -> GrB_UNINITIALIZED_OBJECT; A not square or labels not of size n -> GrB_DIMENSION_MISMATCH; A
+    outside f32 / i32 or labels not i32 -> GrB_NOT_IMPLEMENTED; a built A with entries but no CSR on the device ->
+    GrB_INVALID_OBJECT; no device memory -> GrB_OUT_OF_MEMORY; a grid barrier that gave up -> GrB_PANIC (labels unchanged on every error).  n = 0, an A without entries or W = 0 is a success with
+    labels[v] = v, levels = rounds = 1 and qn = 0.  Returns (info, dict(levels, rounds, moves = accepted proposals,
+    proposals, communities, qn, w, modularity = float(qn) / (float(w) * float(w)) or 0 -- all exact and the same on any number
+    of CUs --, passes, launches = one a level, loop_ms))."""
+    res = _lib.LouvainResult()
+    info = _lib.load().grb_louvain(_h(labels), _h(A), int(weighted), int(max_levels), int(max_rounds), _h(desc), C.byref(res))
+    return info, dict(levels=res.levels, rounds=res.rounds, moves=res.moves, proposals=res.proposals,
+                      communities=res.communities, qn=res.qn, w=res.w, modularity=res.modularity, passes=res.passes,
+                      launches=res.launches, loop_ms=res.loop_ms)
+
+
 GRB_FLOW_CAPACITY, GRB_FLOW_UNIT = 0, 1
 
 

@@ -1404,6 +1404,96 @@ grb_info grb_relabel(grb_vector map, grb_vector labels, int kind, int32_t* count
 grb_info grb_contract(grb_matrix C, grb_vector sizes, grb_matrix A, grb_vector map, grb_binary_op op, int loops,
                       grb_descriptor desc, grb_contract_result* result);
 
+/* Louvain community detection (csrc/louvain.hip): grb_louvain.  The reference has no such driver (graphblas/algorithm/), so
+ * the definition is this header's own; cuGraph, networkx, igraph and Grappolo ship the method.  It is the modularity
+ * optimisation on top of grb_relabel and grb_contract.  The rule below is deterministic, gives the same bits on any number of
+ * CUs, and terminates: it uses exact 64-bit integer arithmetic and integer atomics only, and every accepted round strictly
+ * increases the modularity.
+ *
+ * Input.  A is n x n, f32 or i32, with symmetric structure and values.  weighted = 1 reads the values: an i32 value must be
+ * >= 0, an f32 value a non-negative integer value <= 2^24 (grb_maxflow's rule) with -0.0 = +0.0; anything else (negative,
+ * fractional, NaN, +-inf, above 2^24) is GRB_INVALID_VALUE.  weighted = 0 never reads the values: every stored entry weighs 1.
+ * A stored zero is an entry of weight 0.  A diagonal entry A(v, v) is a loop of that weight.  W = the sum of all stored
+ * weights, the diagonal included, each entry once as stored; W must be <= 2^31 - 1, else GRB_INVALID_VALUE: the bound keeps
+ * every product below in a signed 64-bit integer.  The weights become i32 once, on the device; every coarser level is i32.
+ *
+ * Modularity, as an exact integer.  For a partition c: in(x) = the sum of A(i, j) over the stored entries with
+ * c(i) = c(j) = x; k(v) = the sum of row v with the diagonal; tot(x) = the sum of k(v) over c(v) = x;
+ *   QN = W * sum_x in(x) - sum_x tot(x)^2,   Q = QN / W^2.
+ * QN is invariant under contraction with loops kept and PLUS, so every level can be checked exactly.
+ *
+ * One level works on a graph G with n_G vertices (level 0: A; later: the contraction).  c(v) = v at first, tot(x) = k(x).
+ * Rounds 1, 2, ... are
+ *   1. Propose.  Every vertex v with a non-empty off-diagonal row computes e(v, x) = the sum of G(v, u) over u != v with
+ *      c(u) = x, for its own community a = c(v) and for every neighbouring community.  stay = W e(v, a) - k(v) (tot(a) - k(v)).
+ *      For x != a, gain(x) = W e(v, x) - k(v) tot(x) - stay.  v proposes the x with the largest gain, the smallest x on a
+ *      tie, and only if that gain is > 0: the proposal (v -> d, g).  All of this reads the state at the start of the round.
+ *   2. Claim.  Every proposal claims both a and d.  winner(x) = the claimant with the largest g, the smallest v on a tie.
+ *      K(d) = the sum of k(v) over all proposers to d.
+ *   3. Accept.  (v -> d, g) is accepted iff winner(c(v)) = v, and either winner(d) = v, or winner(d) itself proposes to
+ *      enter d (it is not a vertex leaving d) and g > k(v) (K(d) - k(v)).
+ *   4. Apply.  All accepted moves at once, to c and tot.
+ * A round without proposals ends the level and counts in rounds; so does reaching max_rounds.
+ * Why QN strictly increases: a community with an accepted leaver has no other accepted move touching it, and a destination
+ * has no leaver, so every e, tot and stay a mover used is exact but for its co-entrants; the acceptance test charges every
+ * pair of co-entrants its worst case k k' to a member that passed the test.  The globally best proposal is always accepted:
+ * every round with a proposal moves a vertex, and the level terminates.  (DESIGN.md 5.4s has the derivation.)
+ *
+ * Levels.  After a level map = grb_relabel(c) and G' = grb_contract(G, map, GRB_OP_PLUS, loops = 1) on i32; the assignment
+ * of the original vertices is gathered through map.  The call stops after the first level that accepted no move (it counts
+ * in levels; its partition is the one before it) or after max_levels.  labels(v) = the smallest original vertex number in
+ * v's final community: the convention of grb_cc, grb_scc and grb_msf.
+ *
+ * grb_louvain(labels, A, weighted, max_levels, max_rounds, desc, result): labels is an i32 vector of size n and becomes
+ * dense.  desc may be NULL; no descriptor field is read.  result may be NULL.
+ *
+ * Symmetry follows grb_msf's rule: only the CSR is read.  When A has a CSC of its own, one comparison on the device checks the
+ * CSR against the CSC: pointers and indices, and with weighted = 1 also the values as bits after -0 has been mapped to +0; a
+ * mismatch is GRB_INVALID_VALUE.  An A without a CSC of its own (a product result, the CSR-only matrix format) is taken on the
+ * caller's word: whatever it holds, nothing is read or written out of bounds and every level stops after max_rounds rounds;
+ * the output is then unspecified.
+ *
+ * How: the weights are checked and converted, and W and k summed, by plain launches.  A level is ONE co-resident launch of a
+ * 1024-thread workgroup per CU (GRB_NUM_CU is honoured) whose passes are separated by a grid barrier with bounded spins; the
+ * host reads one record per level.  The propose pass deals the rows by length: up to 8 entries a lane, up to 64 a wave with
+ * all pairs compared, up to 256 a wave and up to 2048 the workgroup with an LDS table of (community, 32-bit weight sum)
+ * pairs, and beyond that a global array of n_G words per long row in flight, after one more barrier.  From the table on, rows
+ * are streamed as 16-byte quads, indices and weights together.  The claim is a 64-bit integer atomicMax of g per touched
+ * community and, after a barrier, a 32-bit atomicMin of v among the holders of the maximum; K(d) an integer atomicAdd (K <= W
+ * fits 32 bits).  The accept pass decides, the apply pass writes c and tot by integer atomics and clears what the round
+ * touched: four barriers a round, five with a long row.  The level's last pass sums in(x) and tot(x)^2.  No floating-point
+ * atomics; nothing is allocated inside a level.  Every vertex is evaluated in every round.  Working memory: 44 bytes per
+ * vertex of a level, 8 per original vertex, 4 per stored entry of A (the i32 weights), for n > 2048 the count arrays (as many
+ * of n words each as fit in 128 MiB, one a CU at most and always at least one, so a single array where n is above 32 M; they
+ * are allocated and zeroed once a call whether or not a row is long), and what grb_contract takes between the levels.  None of the constants has been measured; they mirror grb_cdlp's.
+ * The worst case is a path: chains of equal gains serialise on the smallest-v tie, as in grb_matching with equal weights.
+ *
+ * levels, rounds, moves, proposals, communities, qn, w and modularity are exact and independent of scheduling and of
+ * GRB_NUM_CU.  modularity = (double)qn / ((double)w * (double)w), 0 when w = 0.
+ *
+ * Every error is found before labels is written, and labels keeps what it held.  A null labels or A, or an unbuilt A:
+ * GRB_UNINITIALIZED_OBJECT; A not square or size(labels) != n: GRB_DIMENSION_MISMATCH; labels not i32, or A outside f32 /
+ * i32: GRB_NOT_IMPLEMENTED; an asymmetric A, a bad weight, W > 2^31 - 1, weighted outside {0, 1}, max_levels < 1 or
+ * max_rounds < 1: GRB_INVALID_VALUE; a built A with entries but without CSR arrays on the device: GRB_INVALID_OBJECT, as in
+ * grb_contract; a failed device allocation: GRB_OUT_OF_MEMORY; a grid barrier that gave up: GRB_PANIC,
+ * as in the other one-launch drivers.  n = 0, an A without entries, or W = 0 is a success: labels(v) = v, levels = 1,
+ * rounds = 1, qn = 0, communities = n. */
+typedef struct {
+  int64_t qn;            /* W * sum in(x) - sum tot(x)^2 of the final partition                      */
+  int64_t w;             /* W: the sum of all stored weights                                         */
+  int64_t moves;         /* accepted proposals, all levels                                           */
+  int64_t proposals;     /* proposals, all levels                                                    */
+  double  modularity;    /* (double)qn / ((double)w * (double)w); 0 when w = 0                       */
+  int32_t levels;        /* levels run, the last one that moved nothing included                     */
+  int32_t rounds;        /* rounds of all levels, each level's last one included                     */
+  int32_t communities;   /* distinct values of labels                                                */
+  int32_t passes;        /* grid-wide passes the device ran: implementation-defined, bench only      */
+  int32_t launches;      /* co-resident launches: one a level                                        */
+  float   loop_ms;       /* HIP-event time of the call's device work                                 */
+} grb_louvain_result;     /* 64 bytes */
+grb_info grb_louvain(grb_vector labels, grb_matrix A, int weighted, int max_levels, int max_rounds, grb_descriptor desc,
+                     grb_louvain_result* result);
+
 /* Maximum flow and minimum cut (csrc/maxflow.hip): grb_maxflow.  The reference has no such driver (graphblas/algorithm/), so
  * the definition is this header's own; LAGraph ships the algorithm as LAGr_MaxFlow.
  *
