@@ -87,6 +87,16 @@ class LouvainResult(C.Structure):
                 ("passes", C.c_int32), ("launches", C.c_int32), ("loop_ms", C.c_float)]
 
 
+class WalkResult(C.Structure):
+    _fields_ = [("walkers", C.c_int64), ("steps", C.c_int64), ("dead_ends", C.c_int64), ("launches", C.c_int32),
+                ("loop_ms", C.c_float)]
+
+
+class SampleResult(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("entries", C.c_int64), ("full_rows", C.c_int64), ("launches", C.c_int32),
+                ("loop_ms", C.c_float)]
+
+
 class MaxflowResult(C.Structure):
     _fields_ = [("value", C.c_int64), ("arcs", C.c_int64), ("flow_arcs", C.c_int64), ("sink_side", C.c_int64),
                 ("cut_arcs", C.c_int64), ("cut_capacity", C.c_int64), ("rounds", C.c_int32), ("global_relabels", C.c_int32),
@@ -273,6 +283,8 @@ _SIGS = {
     "grb_relabel": [_vp, _vp, _i, C.POINTER(C.c_int32), _vp],
     "grb_contract": [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(ContractResult)],
     "grb_louvain": [_vp, _vp, _i, _i, _i, _vp, C.POINTER(LouvainResult)],
+    "grb_random_walk": [_vp, _vp, _vp, C.c_int64, _i, _i, C.c_uint32, _vp, C.POINTER(WalkResult)],
+    "grb_sample_neighbors": [_vp, _vp, _vp, _i, _i, C.c_uint32, _vp, C.POINTER(SampleResult)],
     "grb_maxflow": [_vp, _vp, _vp, C.c_int64, C.c_int64, _i, _vp, C.POINTER(MaxflowResult)],
     "grb_bcc": [_vp, _vp, _vp, _i, _vp, C.POINTER(BccResult)],
     "grb_tc_set_product": [_i],

@@ -998,6 +998,71 @@ def louvain(labels, A, weighted, max_levels, max_rounds, desc):
                       launches=res.launches, loop_ms=res.loop_ms)
 
 
+GRB_WALK_UNIFORM, GRB_WALK_WEIGHTED = 0, 1
+
+
+def random_walk(walks, A, starts, length, mode, seed, desc):
+    """grb_random_walk: walks = random walks on A's graph from the vertices in starts, counter-based: every draw is a pure
+    function of (seed, walker, step), so the same inputs give the same bits on any number of CUs.  All arithmetic of the
+    draw is unsigned 32-bit and wraps: mix(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16;
+    draw(seed, a, b) = mix(mix(mix((seed + 0x9e3779b9) ^ a) + b) ^ seed); pick(r, m) = (uint64(r) * uint64(m)) >> 32, a
+    number in 0 .. m - 1.  A is n x n, f32 or i32, directed or not; a stored A(i, j) is the step i -> j, a diagonal entry an
+    ordinary step; only the CSR is read (a product result and the CSR-only format work).  starts: vertex ids (duplicates
+    are different walkers), or None for every vertex 0 .. n - 1 in order; ns = their number.  length >= 0 is the number of
+    steps.  walks is an i32 vector of size ns * (length + 1) that becomes dense, walker-major:
+    walks[w * (length + 1) + t] = walker w's vertex after t steps, walks[w * (length + 1)] = starts[w].  Step t (from 0) of
+    walker w at vertex v, with r = draw(seed, w, t): mode = GRB_WALK_UNIFORM = 0 never reads the values: with d = the stored
+    entries of row v, the next vertex is the column of entry pick(r, d) of the row in stored order.  mode =
+    GRB_WALK_WEIGHTED = 1 reads the values under louvain's rule: i32 >= 0, f32 a non-negative integer value <= 2^24 with
+    -0.0 = +0.0 (negative, fractional, NaN, inf -> GrB_INVALID_VALUE); S(v) = the row's sum must be <= 2^31 - 1 for every
+    row, else GrB_INVALID_VALUE; the next vertex is the column of the first entry whose inclusive prefix sum in stored order
+    exceeds pick(r, S(v)); an entry of weight 0 is never taken.  A dead end is a row with d = 0, or in weighted mode
+    S(v) = 0: the walk stops there, and every later position of that walker is -1.  No descriptor field is read.  A null or
+    unbuilt argument -> GrB_UNINITIALIZED_OBJECT; A not square or size(walks) != ns * (length + 1) ->
+    GrB_DIMENSION_MISMATCH; a start outside 0 .. n - 1 -> GrB_INVALID_INDEX; length < 0, a mode outside {0, 1}, a bad weight
+    or row sum, or ns * (length + 1) > INT32_MAX -> GrB_INVALID_VALUE; walks not i32 or A outside f32 / i32 ->
+    GrB_NOT_IMPLEMENTED; a built A with entries but no CSR on the device -> GrB_INVALID_OBJECT; no device memory ->
+    GrB_OUT_OF_MEMORY (walks unchanged on every error).  ns = 0 is a success with nothing written.  Out of scope:
+    second-order (node2vec) walks and restarts.  Returns (info, dict(walkers = ns, steps = transitions made, summed over the
+    walkers, dead_ends = walkers that stopped early -- exact and the same on any number of CUs --, launches, loop_ms))."""
+    res = _lib.WalkResult()
+    if starts is None:
+        info = _lib.load().grb_random_walk(_h(walks), _h(A), None, 0, int(length), int(mode), int(seed) & 0xffffffff, _h(desc), C.byref(res))
+    else:
+        src = np.ascontiguousarray(starts, dtype=np.int32).ravel()
+        buf = src if src.size else np.zeros(1, np.int32)   # an empty list is no walkers, not "every vertex"
+        info = _lib.load().grb_random_walk(_h(walks), _h(A), buf.ctypes.data, int(src.size), int(length), int(mode),
+                                           int(seed) & 0xffffffff, _h(desc), C.byref(res))
+    return info, dict(walkers=res.walkers, steps=res.steps, dead_ends=res.dead_ends, launches=res.launches, loop_ms=res.loop_ms)
+
+
+_byref = C.byref
+
+
+def sample_neighbors(C, A, seeds, fanout, seed, desc):  # noqa: N803  (C is the result here; ctypes is _byref below)
+    """grb_sample_neighbors: C = a fan-out-limited sample of the rows of A named by seeds, uniform without replacement, with
+    random_walk's counter-based draw(seed, a, b) (its docstring has the arithmetic).  A is nrows x ncols (rectangular is
+    fine), f32 or i32; only the CSR is read.  seeds: row numbers in any order, duplicates allowed; ns = their number.  C is
+    ns x ncols, of A's type.  Row k of C is drawn from row seeds[k] of A, with d its length: if d <= fanout the whole row,
+    otherwise the fanout entries with the smallest draw(seed, k, p), p = 0 .. d - 1 the entry's position in the row.  The
+    key takes the list position k, not the vertex: a seed listed twice is sampled twice, independently.  The kept entries
+    stay in A's stored order (the columns ascend) and carry A's value bits unchanged: stored zeros, -0.0 and NaN are copied,
+    nothing is read as a number.  C gets a CSC by the transposition behind transpose where its format keeps one; C may be
+    A.  No descriptor field is read.  A null or unbuilt argument -> GrB_UNINITIALIZED_OBJECT; C not ns x ncols ->
+    GrB_DIMENSION_MISMATCH; a seed outside 0 .. nrows - 1 -> GrB_INDEX_OUT_OF_BOUNDS; fanout < 1 -> GrB_INVALID_VALUE; the
+    types of A and C not both f32 or both i32 -> GrB_NOT_IMPLEMENTED; a built A with entries but no CSR on the device ->
+    GrB_INVALID_OBJECT; more than INT32_MAX entries or no device memory -> GrB_OUT_OF_MEMORY (C unchanged on every error).
+    ns = 0 gives an empty 0 x ncols C.  Out of scope: weighted sampling without replacement, sampling with replacement,
+    the multi-hop loop (sample, take C's columns as the next seeds, sample again).  Returns (info, dict(rows = ns,
+    entries = nvals(C), full_rows = rows copied whole -- exact and the same on any number of CUs --, launches, loop_ms))."""
+    res = _lib.SampleResult()
+    src = np.ascontiguousarray(seeds if seeds is not None else [], dtype=np.int32).ravel()
+    buf = src if src.size else np.zeros(1, np.int32)
+    info = _lib.load().grb_sample_neighbors(_h(C), _h(A), buf.ctypes.data, int(src.size), int(fanout), int(seed) & 0xffffffff,
+                                            _h(desc), _byref(res))
+    return info, dict(rows=res.rows, entries=res.entries, full_rows=res.full_rows, launches=res.launches, loop_ms=res.loop_ms)
+
+
 GRB_FLOW_CAPACITY, GRB_FLOW_UNIT = 0, 1
 
 

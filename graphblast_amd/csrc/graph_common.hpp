@@ -36,6 +36,18 @@ __device__ __forceinline__ unsigned weight_order(unsigned b, int f32) {
   return value_order(weight_canon(b, 1), 1);
 }
 
+// ---- device: the 32-bit finaliser ------------------------------------------------------------------------------------------
+// a bijection of the 32-bit words that spreads every input bit over the output (matching.hip's hashed priorities, sample.hip's
+// draws).  Its bits are part of both definitions (include/grb_hip.h): they must not change.
+__device__ __forceinline__ unsigned hash_mix32(unsigned x) {
+  x ^= x >> 16;
+  x *= 0x85ebca6bu;
+  x ^= x >> 13;
+  x *= 0xc2b2ae35u;
+  x ^= x >> 16;
+  return x;
+}
+
 // ---- the structural-symmetry check -------------------------------------------------------------------------------------------
 // flag |= 1 when the CSR and the CSC differ (a symmetric matrix has the same arrays both ways): pointers, indices and, with
 // kValues, values as bits with -0 taken as +0

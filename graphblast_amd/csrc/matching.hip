@@ -67,19 +67,11 @@ struct MtArgs {
   MtState* st;
 };
 
-__device__ __forceinline__ unsigned mt_mix(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x85ebca6bu;
-  x ^= x >> 13;
-  x *= 0xc2b2ae35u;
-  x ^= x >> 16;
-  return x;
-}
 // p of the edge {v, u} whose stored bits are w: the smaller goes first
 __device__ __forceinline__ unsigned mt_prio(const MtArgs& a, Index v, Index u, unsigned w) {
   if (a.mode == GRB_MATCH_HASHED) {
     const unsigned lo = (unsigned)(u < v ? u : v), hi = (unsigned)(u < v ? v : u);
-    return mt_mix(mt_mix(lo + a.seed) ^ hi);
+    return hash_mix32(hash_mix32(lo + a.seed) ^ hi);                        // (graph_common.hpp)
   }
   const unsigned o = weight_order(w, a.f32);
   return a.mode == GRB_MATCH_HEAVIEST ? ~o : o;

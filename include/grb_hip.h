@@ -1494,6 +1494,97 @@ typedef struct {
 grb_info grb_louvain(grb_vector labels, grb_matrix A, int weighted, int max_levels, int max_rounds, grb_descriptor desc,
                      grb_louvain_result* result);
 
+/* Random walks and neighbour sampling (csrc/sample.hip): grb_random_walk and grb_sample_neighbors.  The reference has no such
+ * drivers (graphblas/algorithm/), so the definitions are this header's own; cuGraph, DGL and PyTorch Geometric ship the two
+ * operations.  They draw from a graph instead of computing a function of it, and the randomness is counter-based: every draw
+ * is a pure function of (seed, who, when), so the result is the same bits on any number of CUs and in any schedule, and a
+ * host restatement (tests/sample_model.py) is compared for equality, not statistically.
+ *
+ * The draw.  All arithmetic is unsigned 32-bit and wraps.
+ *   mix(x):  x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16   (grb_matching's finaliser)
+ *   draw(seed, a, b) = mix(mix(mix((seed + 0x9e3779b9) ^ a) + b) ^ seed)
+ *   pick(r, m) = (uint64(r) * uint64(m)) >> 32, a number in 0 .. m - 1 for 1 <= m <= 2^31 - 1
+ * mix is a bijection, so for fixed seed and a, draw is a bijection of b: keys drawn for the positions of one row are distinct.
+ *
+ * grb_random_walk(walks, A, starts, ns, length, mode, seed, desc, result).  A is n x n, f32 or i32, directed or not; a stored
+ * A(i, j) is the step i -> j, the direction grb_bfs walks; a diagonal entry is an ordinary step.  Only the CSR is read, so a
+ * product result and the CSR-only format work.  starts is a host array of ns vertices; duplicates are allowed, they are
+ * different walkers.  starts == NULL means every vertex 0 .. n - 1 in order, and ns is ignored (ns = n below).  length >= 0 is
+ * the number of steps.  walks is an i32 vector of size ns * (length + 1) that becomes dense, walker-major:
+ * walks[w * (length + 1) + t] is walker w's vertex after t steps, walks[w * (length + 1)] = starts[w].
+ * Step t (counting from 0) of walker w at vertex v, with r = draw(seed, w, t):
+ *   mode = GRB_WALK_UNIFORM = 0: the values are never read.  With d = the number of stored entries in row v, the next vertex
+ *     is the column of entry pick(r, d) of the row in stored order.
+ *   mode = GRB_WALK_WEIGHTED = 1: the values are read under grb_louvain's rule: an i32 value must be >= 0, an f32 value a
+ *     non-negative integer value <= 2^24 with -0.0 = +0.0; anything else (negative, fractional, NaN, +-inf, above 2^24) is
+ *     GRB_INVALID_VALUE.  S(v) = the sum of row v must be <= 2^31 - 1 for every row, else GRB_INVALID_VALUE.  The next vertex
+ *     is the column of the first entry whose inclusive prefix sum in stored order exceeds pick(r, S(v)).  An entry of weight 0
+ *     is never taken.
+ *   A dead end is a row with d = 0, or in weighted mode S(v) = 0.  The walk stops there, and every later position of that
+ *   walker is -1.
+ * result may be NULL.  walkers = ns; steps = the transitions made, summed over the walkers; dead_ends = the walkers that
+ * stopped early (a walker that merely ends on a vertex without a way out has not): exact, the same on any number of CUs.
+ * Every error is found before walks is written, and walks keeps what it held.  Null or unbuilt objects:
+ * GRB_UNINITIALIZED_OBJECT; A not square, or size(walks) != ns * (length + 1): GRB_DIMENSION_MISMATCH; a start outside
+ * 0 .. n - 1: GRB_INVALID_INDEX, as grb_bc; starts != NULL with ns < 0, length < 0, a mode outside {0, 1}, a bad weight or row
+ * sum, or ns * (length + 1) > INT32_MAX: GRB_INVALID_VALUE; walks not i32, or A not f32 / i32: GRB_NOT_IMPLEMENTED; a built A
+ * with entries but without CSR arrays on the device: GRB_INVALID_OBJECT; a failed device allocation: GRB_OUT_OF_MEMORY.
+ * ns = 0 is a success with nothing written.  desc may be NULL; no descriptor field is read.
+ * How: one lane per walker runs all length steps in registers, plain walker-major stores straight into walks' dense storage
+ * (after the last check), per-wave counts folded into two 64-bit integer atomics a wave.  Weighted mode first builds a u32
+ * array of per-row inclusive prefix sums, 4 bytes per entry, allocated inside the call and freed after it: rows of up to 8
+ * entries by a lane, up to 2048 by a wave, longer ones by the workgroup, from the wave on with 16-byte loads and stores; the
+ * same pass checks the weights and the row sums (in 64 bits) into a flag word the host reads once.  A weighted step is a
+ * binary search in the row's prefix.  Two launches at most, no grid barrier, no floating-point atomics.
+ *
+ * grb_sample_neighbors(C, A, seeds, ns, fanout, seed, desc, result).  A is nrows x ncols (rectangular is fine), f32 or i32;
+ * only the CSR is read.  seeds is a host array of ns row numbers, in any order, duplicates allowed; it may be NULL only when
+ * ns = 0 (else GRB_NULL_POINTER).  C is ns x ncols, of A's type.  Row k of C is drawn from row seeds[k] of A, with d its
+ * length: if d <= fanout, the whole row; otherwise the fanout entries with the smallest draw(seed, k, p), where p = 0 .. d - 1
+ * is the entry's position in the row: uniform sampling without replacement.  The kept entries stay in A's stored order, so
+ * the columns ascend, and carry A's value bits unchanged: stored zeros, -0.0 and NaN are copied, nothing is read as a number.
+ * The key takes the list position k, not the vertex, so a seed listed twice is sampled twice, independently.  C's row
+ * lengths are min(d, fanout), known before any draw: C's pointers come from A's pointers and the library's scan, with no
+ * counting pass.  C gets its orientations by the rule grb_contract's C follows: the CSC by the transposition behind
+ * grb_transpose where the format keeps one, aliased in the CSR-only format.  C may be A: the result is assembled first.
+ * rows = ns, entries = nvals(C), full_rows = the rows copied whole (d <= fanout, empty rows included): exact.
+ * On every error C keeps what it held.  Null or unbuilt objects: GRB_UNINITIALIZED_OBJECT; C not ns x ncols:
+ * GRB_DIMENSION_MISMATCH; a seed outside 0 .. nrows - 1: GRB_INDEX_OUT_OF_BOUNDS, as grb_matrix_extract; fanout < 1, or
+ * ns < 0: GRB_INVALID_VALUE; the types of A and C not both f32 or both i32: GRB_NOT_IMPLEMENTED; a built A with entries but
+ * without CSR arrays on the device: GRB_INVALID_OBJECT; more than INT32_MAX entries in the result, or a failed allocation:
+ * GRB_OUT_OF_MEMORY.  ns = 0 gives an empty 0 x ncols C.
+ * How: keys are recomputed from (seed, k, p) and never loaded or stored.  T, the fanout-th smallest key of a row, is found by
+ * a 32-step bisection on the count of keys <= a midpoint (not a radix select: the count is a ballot and a popcount, and a
+ * lane's or a wave's row needs no LDS; the two have not been measured against each other), then one pass keeps the entries
+ * with key <= T, compacted in stored order by ballot prefix; exactly fanout survive because the keys are distinct.  Rows of
+ * up to 8 entries are taken by a lane (ranks among its own keys, no bisection), up to 512 by a wave with eight keys a lane in
+ * registers, longer ones by one workgroup looping over the row, keys recomputed in each of the 32 steps.  Two host reads.
+ *
+ * Out of scope: second-order (node2vec p / q) walks; restarts; weighted sampling without replacement (its usual keys need
+ * log, which is not the same bits on the host and the device); sampling with replacement; the multi-hop loop (a caller
+ * samples, takes the columns of C as the next seeds, and samples again).  None of the constants has been measured against an
+ * alternative. */
+#define GRB_WALK_UNIFORM 0
+#define GRB_WALK_WEIGHTED 1
+typedef struct {
+  int64_t walkers;       /* ns                                                                       */
+  int64_t steps;         /* transitions made, summed over the walkers                                */
+  int64_t dead_ends;     /* walkers that stopped before their last step                              */
+  int32_t launches;      /* kernels launched: the walk, and in weighted mode the prefix pass         */
+  float   loop_ms;       /* HIP-event time of the call's device work                                 */
+} grb_walk_result;        /* 32 bytes */
+grb_info grb_random_walk(grb_vector walks, grb_matrix A, const grb_index* starts, int64_t ns, int length, int mode, uint32_t seed,
+                         grb_descriptor desc, grb_walk_result* result);
+typedef struct {
+  int64_t rows;          /* ns                                                                       */
+  int64_t entries;       /* nvals(C)                                                                 */
+  int64_t full_rows;     /* rows copied whole: d <= fanout                                           */
+  int32_t launches;      /* kernels launched for C's CSR: the lengths, the scan, the rows            */
+  float   loop_ms;       /* HIP-event time of the call's device work, the CSC included               */
+} grb_sample_result;      /* 32 bytes */
+grb_info grb_sample_neighbors(grb_matrix C, grb_matrix A, const grb_index* seeds, grb_index ns, int fanout, uint32_t seed,
+                              grb_descriptor desc, grb_sample_result* result);
+
 /* Maximum flow and minimum cut (csrc/maxflow.hip): grb_maxflow.  The reference has no such driver (graphblas/algorithm/), so
  * the definition is this header's own; LAGraph ships the algorithm as LAGr_MaxFlow.
  *
